@@ -12,8 +12,14 @@ A "step" is one pass of the hot path over one batch of synthetic frames already 
   --config res50            configs[0]: cfgs/res50.yml, ONE 600x1000 frame, Faster-RCNN forward + SGG_emb head forward
                             (the reference's CPU-runnable plumbing case, here on the GPU and checked against the oracle).
 
-Prints ONE JSON line on rank 0 (the contract of the task brief).  The default run measures the headline and, single
-GPU only, adds the configs[2] measurement (own steps, own roofline block) under "also".
+Prints ONE JSON line on rank 0 (the contract of the task brief).  A plain run measures the headline only: set-up, --warmup
+steps, --steps timed steps, the line (``value``, ``ms_per_step`` = milliseconds per timed step).  --full adds everything
+else: the roofline blocks (eager steps profiled with HIP events), and for the single-GPU sgg config the "also" measurements
+(the loader-fed step, the ROI / NMS ops and roofline_hbm, configs[2], the test loops) and the CPU baseline.
+
+--dump-outputs DIR writes what the timed path computed in its last step as DIR/<name>.npy (float32, float64 for integer
+data; a fixed, seeded sample of the larger arrays, 64 MB at most): the loss(es), the trained parameters after the step's
+update and, for the relation step, the backbone's feature maps.  The inputs are seeded: two builds compare output for output.
 
 --gpus N without a torchrun environment starts its own N ranks (one process per GPU, RCCL over xGMI, rendezvous on
 127.0.0.1) and exits non-zero if any rank fails to come up; under torchrun (RANK set) it is one of the ranks.
@@ -24,6 +30,7 @@ import os
 import subprocess
 import sys
 import time
+import zlib
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
@@ -44,12 +51,17 @@ def parse():
     ap.add_argument("--config", default="sgg", choices=["sgg", "instance_styled", "joint", "res50"])
     ap.add_argument("--data", default="resident", choices=["resident", "loader", "loader_u8"],
                     help="resident: one synthetic minibatch resident in HBM (the headline); loader: roibatchLoader minibatches of "
-                         "varying size staged from pinned host memory every step (config sgg; also reported beside the headline)")
+                         "varying size staged from pinned host memory every step (config sgg; with --full also reported beside the "
+                         "headline)")
     ap.add_argument("--no-graph", action="store_true", help="launch eagerly instead of replaying a HIP graph")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-also", action="store_true", help="headline only: skip the configs[2] measurement")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: roofline blocks, the 'also' legs, the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-also", action="store_true", help="with --full: skip the 'also' measurements")
     ap.add_argument("--layers", type=int, default=101)
-    ap.add_argument("--dump-launches", default="", help="write one line per GEMM launch of a profiled step")
+    ap.add_argument("--dump-launches", default="", help="with --full: write one line per GEMM launch of a profiled step")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the timed path computed in its last step as DIR/<name>.npy")
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher / rendezvous rehearsal on the CPU (gloo): no GPU work, prints the line with dry_run")
     return ap.parse_args()
@@ -287,6 +299,54 @@ def cpu_baseline_stages(threads):
 def train_mod():
     from i2vsgg_amd import train
     return train
+
+
+# ----------------------------------------------------------------------------- --dump-outputs
+DUMP_MAX_BYTES = 64 << 20
+_OUTPUTS = {}
+
+
+def _host(t, cap, name):
+    """One output on the host: float32 (float64 for float64 and integer data), as a fixed sample of ``cap`` elements of its
+    flattened form when larger (seeded by the name: the same positions in every run)."""
+    import numpy as np
+    import torch
+    t = t.detach()
+    if cap is not None and t.numel() > cap:
+        idx = np.unique(np.random.default_rng(zlib.crc32(name.encode())).integers(0, t.numel(), cap))
+        t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+    t = t.cpu()
+    return t.double().numpy() if (t.dtype == torch.float64 or not t.is_floating_point()) else t.float().numpy()
+
+
+def keep_outputs(a, rank, fn):
+    """--dump-outputs: ``fn() -> {name: tensor or (tensor, cap)}``, what the timed path computed in its last step, copied to
+    the host right behind the timed region (before a --full measurement runs more steps on the same objects)."""
+    if not a.dump_outputs or rank != 0:
+        return
+    import torch
+    torch.cuda.synchronize()
+    for name, v in fn().items():
+        t, cap = v if isinstance(v, tuple) else (v, None)
+        _OUTPUTS[name] = _host(t, cap, name)
+
+
+def param_outputs(named, cap=None, budget=None):
+    """The trained parameters (after the last step's update); ``budget`` elements spread evenly over them when given."""
+    named = [(n, p) for n, p in named if p.requires_grad]
+    if budget is not None:
+        cap = max(1024, budget // max(len(named), 1))
+    return {n: (p, cap) for n, p in named}
+
+
+def write_outputs(d):
+    import numpy as np
+    total = sum(v.nbytes for v in _OUTPUTS.values())
+    if total > DUMP_MAX_BYTES:
+        raise RuntimeError("--dump-outputs: %d bytes over the %d-byte limit" % (total, DUMP_MAX_BYTES))
+    os.makedirs(d, exist_ok=True)
+    for name, v in sorted(_OUTPUTS.items()):
+        np.save(os.path.join(d, name + ".npy"), v)
 
 
 # ----------------------------------------------------------------------------- measurement helpers
@@ -553,8 +613,40 @@ def run_sgg(a, rank, world, dev, frames_per_rank=2):
     step = train.SGGEmbStep(net, frames_per_rank, seed=1 + rank, device=dev, use_graph=not a.no_graph)
     graphed = step.capture(warmup=2)
     elapsed = timed_steps(step, a.warmup, a.steps, dev)
+    keep_outputs(a, rank, lambda: dict(loss=step.loss.reshape(1), fmap=step.fmap, **param_outputs(
+        [(n, p) for n, p in net.named_parameters() if n.startswith("vrd.")], cap=1 << 20)))
     loss = float(step.loss)
+    tp = getattr(step, "tp", False)
+    line = {
+        "metric": "frames/sec (600x1000, 32 ROI/frame)", "value": world * frames_per_rank * a.steps / elapsed,
+        "unit": "frames/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
+        "ms_per_step": 1e3 * elapsed / a.steps, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "f32", "data": "synthetic",
+        "config": {"workload": "BASELINE.json configs[%d]: cfgs/res101.yml, SGG_emb fwd+bwd+SGD, %d frames/GPU "
+                               "600x1000, 32 boxes + 32 pairs/frame, ResNet-%d C4" % (3 if world > 1 else 1, frames_per_rank, a.layers),
+                   "frames_per_gpu": frames_per_rank, "global_frames": world * frames_per_rank,
+                   "hip_graph": bool(graphed), "graph_error": step.graph_error,
+                   "parallelism": ("dp%d (frames sharded) + vrd.fc6 cut by output columns across the ranks: RCCL all-reduce of the "
+                                   "other 84 MB of gradients, 30 MB of activation gathers for fc6" % world) if tp
+                   else "dp%d (frames sharded, RCCL all-reduce of vrd grads)" % world,
+                   "schedule": (("one graph per step: [head fwd+bwd (+ gradient exchange) + SGD of batch k] beside [stem..layer3[:%d] "
+                                 "of batch k+2, both frames per launch] beside [layer3[%d:] of batch k+1]; every step = 1 backbone pass "
+                                 "(its two halves on consecutive minibatches) + 1 head pass + 1 update, all inside the timed region"
+                                 % (step.cut, step.cut)) if step.stage_split else
+                                ("one graph per step: [head fwd+bwd (+ gradient exchange) + SGD of batch k] beside the backbone fwd "
+                                 "of batch k+1 (one graph branch per frame); every step = 1 backbone pass + 1 head pass + 1 update, all "
+                                 "inside the timed region")) if step.overlap
+                   else "one graph per step: backbone fwd, head fwd+bwd, fused wgrad+SGD" if graphed else "eager launches",
+                   "loss": loss},
+    }
+    if a.full:
+        line["roofline"] = sgg_roofline(a, rank, dev, step, elapsed)
+    return line, step, net
 
+
+def sgg_roofline(a, rank, dev, step, elapsed):
+    """--full: the roofline block of the relation step, from eager steps of the same objects profiled with HIP events."""
+    import re
     # ---- roofline of the dominant kernel: conv_igemm_f32 (MFMA-bound)
     n_prof = 3
     pp, step._pipelined = step._pipelined, False          # the profiled steps are sequential eager steps of the same objects
@@ -584,68 +676,44 @@ def run_sgg(a, rank, world, dev, frames_per_rank=2):
     achieved = f_gemm / max(t_gemm, 1e-12) / 1e12
     # algorithmic bytes of EVERY conv_gemm_f32 launch of a step, for the comparison with the PMC traffic (which averages over
     # all launches of the kernel): the pointwise calls + the batched plane GEMM inside every Winograd call
-    import re
     wino = [r for r in rec if "winograd" in r["desc"] and "gemmMB=" in r["desc"]]
     b_wino = sum(float(re.search(r"gemmMB=([0-9.]+)", r["desc"]).group(1)) * 1e6 for r in wino)
     n_all = max((len(gemm) + len(wino)) // n_prof, 1)
     b_all = (b_gemm + b_wino) / n_prof / n_all
-    tp = getattr(step, "tp", False)
-    line = {
-        "metric": "frames/sec (600x1000, 32 ROI/frame)", "value": world * frames_per_rank * a.steps / elapsed,
-        "unit": "frames/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
-        "ms_per_step": 1e3 * elapsed / a.steps, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": "f32", "data": "synthetic",
-        "config": {"workload": "BASELINE.json configs[%d]: cfgs/res101.yml, SGG_emb fwd+bwd+SGD, %d frames/GPU "
-                               "600x1000, 32 boxes + 32 pairs/frame, ResNet-%d C4" % (3 if world > 1 else 1, frames_per_rank, a.layers),
-                   "frames_per_gpu": frames_per_rank, "global_frames": world * frames_per_rank,
-                   "hip_graph": bool(graphed), "graph_error": step.graph_error,
-                   "parallelism": ("dp%d (frames sharded) + vrd.fc6 cut by output columns across the ranks: RCCL all-reduce of the "
-                                   "other 84 MB of gradients, 30 MB of activation gathers for fc6" % world) if tp
-                   else "dp%d (frames sharded, RCCL all-reduce of vrd grads)" % world,
-                   "schedule": (("one graph per step: [head fwd+bwd (+ gradient exchange) + SGD of batch k] beside [stem..layer3[:%d] "
-                                 "of batch k+2, both frames per launch] beside [layer3[%d:] of batch k+1]; every step = 1 backbone pass "
-                                 "(its two halves on consecutive minibatches) + 1 head pass + 1 update, all inside the timed region"
-                                 % (step.cut, step.cut)) if step.stage_split else
-                                ("one graph per step: [head fwd+bwd (+ gradient exchange) + SGD of batch k] beside the backbone fwd "
-                                 "of batch k+1 (one graph branch per frame); every step = 1 backbone pass + 1 head pass + 1 update, all "
-                                 "inside the timed region")) if step.overlap
-                   else "one graph per step: backbone fwd, head fwd+bwd, fused wgrad+SGD" if graphed else "eager launches",
-                   "loss": loss},
-        "roofline": {"bound": "mfma", "kernel": "conv_gemm_f32 (pointwise bottleneck layers and the other plain GEMMs it serves; one "
-                                                "launch per call)",
-                     "achieved": achieved, "peak": MFMA_F32_PEAK_TFLOPS, "unit": "TFLOP/s",
-                     "frac": achieved / MFMA_F32_PEAK_TFLOPS, "traffic": traffic, "traffic_source": traffic_src,
-                     "note": ("achieved = 2*M*N*K of every conv_gemm_f32 launch of a step / the summed launch durations (HIP events "
-                              "on the launch stream around every call of %d eager steps of the same objects); all MACs are "
-                              "executed MACs.  all_conv = every convolution forward / data-gradient call of the step "
-                              "(Winograd layers included with their transform kernels)") % n_prof,
-                     "launches_per_step": n_gemm, "avg_launch_us": 1e6 * t_gemm / max(len(gemm), 1),
-                     "algorithmic_bytes_per_launch": b_all, "launches_per_step_incl_winograd_planes": n_all,
-                     "traffic_over_algorithmic": (traffic / b_all) if traffic else None,
-                     "algorithmic_bytes_per_pointwise_launch": b_gemm / n_prof / n_gemm,
-                     "gflop_per_step": f_gemm / n_prof / 1e9,
-                     "all_conv": {"ms_per_step": 1e3 * t_conv / n_prof, "launches_per_step": len(conv) // n_prof,
-                                  "executed_tflops": f_exec / t_conv / 1e12,
-                                  "executed_frac": f_exec / t_conv / 1e12 / MFMA_F32_PEAK_TFLOPS,
-                                  "algorithmic_tflops": f_alg / t_conv / 1e12,
-                                  "algorithmic_frac": f_alg / t_conv / 1e12 / MFMA_F32_PEAK_TFLOPS,
-                                  "gflop_executed_per_step": f_exec / n_prof / 1e9,
-                                  "gflop_algorithmic_per_step": f_alg / n_prof / 1e9},
-                     "by_kind": by_kind(rec, n_prof)},
-    }
+    roof = {"bound": "mfma", "kernel": "conv_gemm_f32 (pointwise bottleneck layers and the other plain GEMMs it serves; one "
+                                       "launch per call)",
+            "achieved": achieved, "peak": MFMA_F32_PEAK_TFLOPS, "unit": "TFLOP/s",
+            "frac": achieved / MFMA_F32_PEAK_TFLOPS, "traffic": traffic, "traffic_source": traffic_src,
+            "note": ("achieved = 2*M*N*K of every conv_gemm_f32 launch of a step / the summed launch durations (HIP events "
+                     "on the launch stream around every call of %d eager steps of the same objects); all MACs are "
+                     "executed MACs.  all_conv = every convolution forward / data-gradient call of the step "
+                     "(Winograd layers included with their transform kernels)") % n_prof,
+            "launches_per_step": n_gemm, "avg_launch_us": 1e6 * t_gemm / max(len(gemm), 1),
+            "algorithmic_bytes_per_launch": b_all, "launches_per_step_incl_winograd_planes": n_all,
+            "traffic_over_algorithmic": (traffic / b_all) if traffic else None,
+            "algorithmic_bytes_per_pointwise_launch": b_gemm / n_prof / n_gemm,
+            "gflop_per_step": f_gemm / n_prof / 1e9,
+            "all_conv": {"ms_per_step": 1e3 * t_conv / n_prof, "launches_per_step": len(conv) // n_prof,
+                         "executed_tflops": f_exec / t_conv / 1e12,
+                         "executed_frac": f_exec / t_conv / 1e12 / MFMA_F32_PEAK_TFLOPS,
+                         "algorithmic_tflops": f_alg / t_conv / 1e12,
+                         "algorithmic_frac": f_alg / t_conv / 1e12 / MFMA_F32_PEAK_TFLOPS,
+                         "gflop_executed_per_step": f_exec / n_prof / 1e9,
+                         "gflop_algorithmic_per_step": f_alg / n_prof / 1e9},
+            "by_kind": by_kind(rec, n_prof)}
     # the whole step against the matrix pipe: every GEMM-shaped launch of a step (backbone, head forward, data and filter
     # gradients, fused updates), executed MACs (Winograd F(4x4,3x3) runs 1/4 of the direct count) / the TIMED ms per step
     wf = lambda r: 0.25 if "winograd F4" in r["desc"] else 4.0 / 9.0 if "winograd" in r["desc"] else 1.0   # noqa: E731
     g_exec = sum(r["flops"] * wf(r) for r in rec) / n_prof / 1e9
     g_alg = sum(r["flops"] for r in rec) / n_prof / 1e9
     ms = 1e3 * elapsed / a.steps
-    line["roofline"]["step"] = {"gflop_executed_per_step": g_exec, "gflop_algorithmic_per_step": g_alg, "ms_per_step": ms,
-                                "executed_tflops": g_exec / ms, "frac": g_exec / ms / MFMA_F32_PEAK_TFLOPS,
-                                "algorithmic_frac": g_alg / ms / MFMA_F32_PEAK_TFLOPS,
-                                "note": "every GEMM-shaped launch of one step / the timed ms per step of the replayed graph; the "
-                                        "fc6 path (forward 0.43 ms + fused update 0.79 ms of kernel time for 4.1 GB) is HBM-bound, "
-                                        "not MFMA-bound: profiles/r05_step_budget.txt has the per-kind budget"}
-    return line, step, net
+    roof["step"] = {"gflop_executed_per_step": g_exec, "gflop_algorithmic_per_step": g_alg, "ms_per_step": ms,
+                    "executed_tflops": g_exec / ms, "frac": g_exec / ms / MFMA_F32_PEAK_TFLOPS,
+                    "algorithmic_frac": g_alg / ms / MFMA_F32_PEAK_TFLOPS,
+                    "note": "every GEMM-shaped launch of one step / the timed ms per step of the replayed graph; the "
+                            "fc6 path (forward 0.43 ms + fused update 0.79 ms of kernel time for 4.1 GB) is HBM-bound, "
+                            "not MFMA-bound: profiles/r05_step_budget.txt has the per-kind budget"}
+    return roof
 
 
 # ----------------------------------------------------------------------------- configs[1] fed by the data layer
@@ -699,19 +767,21 @@ def run_sgg_loader(a, rank, world, dev, frames_per_rank=2, n_batches=8, u8=False
     bubbles = step.n_bubbles
     elapsed = timed_steps(fn, a.warmup, a.steps, dev)
     assert step.n_bubbles == bubbles, "a timed call ran no head"
+    keep_outputs(a, rank, lambda: dict(loss=step.loss.reshape(1), fmap=step.fmap, **param_outputs(
+        [(n, p) for n, p in net.named_parameters() if n.startswith("vrd.")], cap=1 << 20)))
     sizes = sorted({hw(d) for d in batches})
-    # The same graphs with their minibatch RESIDENT (staged once, replayed): what the loader-fed step would take if staging cost
-    # nothing -- the loader's frames are not 600x1000 (five resolutions, 460-640 kpixel), so the headline's resident step is not
-    # the yardstick.  Mean over the minibatches in the order the timed loop visits them.
+    # --full: the same graphs with their minibatch RESIDENT (staged once, replayed): what the loader-fed step would take if staging
+    # cost nothing -- the loader's frames are not 600x1000 (five resolutions, 460-640 kpixel), so the headline's resident step is
+    # not the yardstick.  Mean over the minibatches in the order the timed loop visits them.
     res_ms = {}
-    for d in batches:
-        if hw(d) in res_ms:
-            continue
-        stage(d)
-        for _ in range(1 + step.lag):     # the pipeline holds only this minibatch from here on
-            step()
-        res_ms[hw(d)] = 1e3 * timed_steps(step, 2, max(a.steps // 2, 5), dev) / max(a.steps // 2, 5)
-    resident_same = sum(res_ms[hw(d)] for d in batches) / len(batches)
+    if a.full:
+        for d in batches:
+            if hw(d) in res_ms:
+                continue
+            stage(d)
+            for _ in range(1 + step.lag):     # the pipeline holds only this minibatch from here on
+                step()
+            res_ms[hw(d)] = 1e3 * timed_steps(step, 2, max(a.steps // 2, 5), dev) / max(a.steps // 2, 5)
     rels = net.vrd.source_gt_rels
     nb = [sum(len(rels[p.split("/")[-1]]["boxes"]) for p in d[4]) for d in batches]
     line = {
@@ -729,11 +799,13 @@ def run_sgg_loader(a, rank, world, dev, frames_per_rank=2, n_batches=8, u8=False
                    "frames_per_gpu": frames_per_rank, "hip_graph": bool(graphed), "graph_error": step.graph_error,
                    "graphs": sum(1 for fs in step.shapes.values() if fs.graph), "frame_sizes": sizes,
                    "head_capacity_rows": [step.cap_boxes, step.cap_pairs],
-                   "loader_cpu_ms_per_minibatch": loader_ms, "loss": float(step.loss),
-                   "resident_ms_per_step_at_these_sizes": resident_same,
-                   "resident_ms_by_size": {"%dx%d" % k: v for k, v in sorted(res_ms.items())},
-                   "staging_cost_ms_per_step": 1e3 * elapsed / a.steps - resident_same},
+                   "loader_cpu_ms_per_minibatch": loader_ms, "loss": float(step.loss)},
     }
+    if a.full:
+        resident_same = sum(res_ms[hw(d)] for d in batches) / len(batches)
+        line["config"].update(resident_ms_per_step_at_these_sizes=resident_same,
+                              resident_ms_by_size={"%dx%d" % k: v for k, v in sorted(res_ms.items())},
+                              staging_cost_ms_per_step=1e3 * elapsed / a.steps - resident_same)
     return line, step, net
 
 
@@ -800,7 +872,29 @@ def run_instance_styled(a, rank, world, dev, steps, warmup, frames_per_rank=4):
         for _ in range(2):
             step()
     elapsed = timed_steps(step, warmup, steps, dev)
+    keep_outputs(a, rank, lambda: dict({"loss." + k: torch.as_tensor(v).reshape(1) for k, v in step.losses.items()},
+                                       **param_outputs(net.named_parameters(), budget=6 << 20)))
     losses = {k: float(v) for k, v in step.losses.items()}
+    roof = isd_roofline(a, rank, dev, step) if a.full else None
+    line = {
+        "metric": "frames/sec (600x1000, 32 ROI/frame)", "value": world * 2 * frames_per_rank * steps / elapsed,
+        "unit": "frames/s", "n_gpus": world, "steps": steps, "warmup": warmup, "ms_per_step": 1e3 * elapsed / steps,
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        "config": {"workload": "BASELINE.json configs[2]: cfgs/res101.yml, instance_styleD D+G adversarial step, %d source + %d "
+                               "target frames/GPU 600x1000, 32 ROI/frame, ResNet-%d, layer1-3 + heads trained" % (
+                                   frames_per_rank, frames_per_rank, a.layers),
+                   "frames_per_gpu": 2 * frames_per_rank, "hip_graph": bool(graphed),
+                   "graph_error": getattr(step, "graph_error", None),
+                   "parallelism": "dp%d (frames sharded, RCCL all-reduce of 202 MB of gradients)" % world,
+                   "losses": losses, "max_mem_GB": torch.cuda.max_memory_allocated(dev) / 2 ** 30},
+    }
+    if roof is not None:
+        line["roofline"] = roof
+    return line, step, net
+
+
+def isd_roofline(a, rank, dev, step):
+    """--full: the roofline block of the configs[2] step, from eager steps of the same objects profiled with HIP events."""
     n_prof = 2
     rec = profile_eager(step.eager_step if hasattr(step, "eager_step") else step, n_prof, dev)
     if a.dump_launches and rank == 0:
@@ -819,26 +913,13 @@ def run_instance_styled(a, rank, world, dev, steps, warmup, frames_per_rank=4):
     # the PMC passes of THIS configuration (tools/profile_bench.sh isd), not the headline's (whose conv_wgrad2_f32 launches
     # are the relation head's skinny GEMMs)
     traffic, traffic_src = pmc_traffic("conv_wgrad2_f32", ("r06_instance_styled_pmc_summary.json", "r05_instance_styled_pmc_summary.json", "r04_instance_styled_pmc_summary.json", "r03_instance_styled_pmc_summary.json", "r02_instance_styled_pmc_summary.json"))
-    line = {
-        "metric": "frames/sec (600x1000, 32 ROI/frame)", "value": world * 2 * frames_per_rank * steps / elapsed,
-        "unit": "frames/s", "n_gpus": world, "steps": steps, "warmup": warmup, "ms_per_step": 1e3 * elapsed / steps,
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-        "config": {"workload": "BASELINE.json configs[2]: cfgs/res101.yml, instance_styleD D+G adversarial step, %d source + %d "
-                               "target frames/GPU 600x1000, 32 ROI/frame, ResNet-%d, layer1-3 + heads trained" % (
-                                   frames_per_rank, frames_per_rank, a.layers),
-                   "frames_per_gpu": 2 * frames_per_rank, "hip_graph": bool(graphed),
-                   "graph_error": getattr(step, "graph_error", None),
-                   "parallelism": "dp%d (frames sharded, RCCL all-reduce of 202 MB of gradients)" % world,
-                   "losses": losses, "max_mem_GB": torch.cuda.max_memory_allocated(dev) / 2 ** 30},
-        "roofline": {"bound": "mfma", "kernel": "conv_wgrad2_f32 (every filter gradient of the step; executed MACs, the "
-                                                "Winograd-domain 3x3 layers included with their transform kernels)", "achieved": achieved,
-                     "peak": MFMA_F32_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": achieved / MFMA_F32_PEAK_TFLOPS,
-                     "algorithmic_tflops": f_wg / max(t_wg, 1e-12) / 1e12,
-                     "traffic": traffic, "traffic_source": traffic_src,
-                     "algorithmic_bytes_per_launch": b_wg / max(len(wg), 1), "launches_per_step": len(wg) // n_prof,
-                     "avg_launch_us": 1e6 * t_wg / max(len(wg), 1), "by_kind": by_kind(rec, n_prof)},
-    }
-    return line, step, net
+    return {"bound": "mfma", "kernel": "conv_wgrad2_f32 (every filter gradient of the step; executed MACs, the "
+                                       "Winograd-domain 3x3 layers included with their transform kernels)", "achieved": achieved,
+            "peak": MFMA_F32_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": achieved / MFMA_F32_PEAK_TFLOPS,
+            "algorithmic_tflops": f_wg / max(t_wg, 1e-12) / 1e12,
+            "traffic": traffic, "traffic_source": traffic_src,
+            "algorithmic_bytes_per_launch": b_wg / max(len(wg), 1), "launches_per_step": len(wg) // n_prof,
+            "avg_launch_us": 1e6 * t_wg / max(len(wg), 1), "by_kind": by_kind(rec, n_prof)}
 
 
 # ----------------------------------------------------------------------------- configs[4]
@@ -860,20 +941,11 @@ def run_joint(a, rank, world, dev, frames_per_rank=4):
         dstep()
         sstep()
     elapsed = timed_steps(both, a.warmup, a.steps, dev)
-    # ---- roofline of the dominant kernel of the joint step: every conv_gemm_f32 launch of both halves (the pointwise layers of
-    # the detector's trained trunk, forward and data gradient, and of the relation net's frozen trunk), HIP events around every
-    # call of eager steps of the same objects
-    n_prof = 2
-    pp, sstep._pipelined = sstep._pipelined, False
-
-    def eager_both():
-        dstep.eager_step()
-        sstep._body()
-    rec = profile_eager(eager_both, n_prof, dev)
-    sstep._pipelined = pp
-    gemm = [r for r in rec if r["tag"] in ("fwd", "dgrad") and ("[gemm]" in r["desc"] or "+epi" in r["desc"]) and "winograd" not in r["desc"]]
-    t_gemm, f_gemm = sum(r["t"] for r in gemm), sum(r["flops"] for r in gemm)
-    achieved = f_gemm / max(t_gemm, 1e-12) / 1e12
+    keep_outputs(a, rank, lambda: {
+        **{"det.loss." + k: torch.as_tensor(v).reshape(1) for k, v in dstep.losses.items()}, "sgg.loss": sstep.loss.reshape(1),
+        **param_outputs([("det." + n, p) for n, p in det.named_parameters()], budget=4 << 20),
+        **param_outputs([("sgg." + n, p) for n, p in sgg.named_parameters() if n.startswith("vrd.")], budget=2 << 20)})
+    roof = joint_roofline(dev, dstep, sstep) if a.full else None
     line = {
         "metric": "frames/sec (600x1000, 32 ROI/frame)", "value": world * frames_per_rank * a.steps / elapsed,
         "unit": "frames/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": 1e3 * elapsed / a.steps,
@@ -886,15 +958,34 @@ def run_joint(a, rank, world, dev, frames_per_rank=4):
                    "loss_sgg": float(sstep.loss), "loss_det": float(dstep.losses["total"]),
                    "losses_det": {k: float(v) for k, v in dstep.losses.items()},
                    "max_mem_GB": torch.cuda.max_memory_allocated(dev) / 2 ** 30},
-        "roofline": {"bound": "mfma", "kernel": "conv_gemm_f32 / conv_igemm_f32 pointwise launches of both halves (forward and fused data "
-                                                "gradient of the 1x1 layers; one launch per call)",
-                     "achieved": achieved, "peak": MFMA_F32_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": achieved / MFMA_F32_PEAK_TFLOPS,
-                     "traffic": None, "launches_per_step": len(gemm) // n_prof, "avg_launch_us": 1e6 * t_gemm / max(len(gemm), 1),
-                     "gflop_per_step": f_gemm / n_prof / 1e9, "by_kind": by_kind(rec, n_prof),
-                     "note": "2*M*N*K of the launches / their summed durations (HIP events on the launch stream, %d eager joint "
-                             "steps of the same objects); the timed region replays the two captured graphs" % n_prof},
     }
+    if roof is not None:
+        line["roofline"] = roof
     return line, (dstep, sstep), (det, sgg)
+
+
+def joint_roofline(dev, dstep, sstep):
+    """--full: the roofline block of the joint step.  The dominant kernel: every conv_gemm_f32 launch of both halves (the
+    pointwise layers of the detector's trained trunk, forward and data gradient, and of the relation net's frozen trunk), HIP
+    events around every call of eager steps of the same objects."""
+    n_prof = 2
+    pp, sstep._pipelined = sstep._pipelined, False
+
+    def eager_both():
+        dstep.eager_step()
+        sstep._body()
+    rec = profile_eager(eager_both, n_prof, dev)
+    sstep._pipelined = pp
+    gemm = [r for r in rec if r["tag"] in ("fwd", "dgrad") and ("[gemm]" in r["desc"] or "+epi" in r["desc"]) and "winograd" not in r["desc"]]
+    t_gemm, f_gemm = sum(r["t"] for r in gemm), sum(r["flops"] for r in gemm)
+    achieved = f_gemm / max(t_gemm, 1e-12) / 1e12
+    return {"bound": "mfma", "kernel": "conv_gemm_f32 / conv_igemm_f32 pointwise launches of both halves (forward and fused data "
+                                       "gradient of the 1x1 layers; one launch per call)",
+            "achieved": achieved, "peak": MFMA_F32_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": achieved / MFMA_F32_PEAK_TFLOPS,
+            "traffic": None, "launches_per_step": len(gemm) // n_prof, "avg_launch_us": 1e6 * t_gemm / max(len(gemm), 1),
+            "gflop_per_step": f_gemm / n_prof / 1e9, "by_kind": by_kind(rec, n_prof),
+            "note": "2*M*N*K of the launches / their summed durations (HIP events on the launch stream, %d eager joint "
+                    "steps of the same objects); the timed region replays the two captured graphs" % n_prof}
 
 
 # ----------------------------------------------------------------------------- configs[0]
@@ -912,13 +1003,19 @@ def run_res50(a, rank, world, dev):
     imd, infod, gtd, nbd = to(im), to(info), to(gt), to(nb)
     sstep = train.SGGEmbStep(sgg, 1, seed=0, device=dev, n_boxes=8, n_pairs=8, use_graph=False)
 
+    last = []
+
     def fwd():
         with torch.no_grad():
             out = det(imd, infod, gtd, nbd)
             fmap = sgg.RCNN_base(sstep.im)
             score, _ = sgg.vrd.forward_device(fmap, sstep.boxes, sstep.relb, sstep.masks, sstep.ixs, sstep.ixo)
+        last[:] = [out, score]
         return out, score
     elapsed = timed_steps(fwd, a.warmup, a.steps, dev)
+    names = ("rois", "cls_prob", "bbox_pred")          # the detector's eval outputs (faster_rcnn_instance_styleD_bilinear.py)
+    keep_outputs(a, rank, lambda: dict({(names[i] if i < len(names) else "det_out%d" % i): (t, 1 << 20)
+                                        for i, t in enumerate(last[0]) if torch.is_tensor(t)}, rel_score=last[1]))
     out, score = fwd()
     line = {
         "metric": "frames/sec (600x1000, 32 ROI/frame)", "value": world * a.steps / elapsed, "unit": "frames/s",
@@ -980,11 +1077,12 @@ def main():
     elif a.config == "sgg":
         line, step, net = run_sgg(a, rank, world, dev)
         keep += [step, net]
-        if world == 1 and not a.no_also:
+        if world == 1 and a.full and not a.no_also:
             # Secondary measurements under the same driver clock.  Each is guarded: whatever happens in one of them, the headline
             # line above is printed (a failure is recorded under "also" with its message).
             line["also"] = {}
             pick = lambda ld: {k: ld[k] for k in ("value", "unit", "ms_per_step", "steps", "data", "config")}
+            sub = argparse.Namespace(**dict(vars(a), dump_outputs=""))      # --dump-outputs holds the headline's outputs
 
             def also(name, fn):
                 try:
@@ -996,14 +1094,14 @@ def main():
 
             def loader(u8):
                 # the same step fed by the data layer (varying minibatch sizes, staged from the host every step)
-                ld, s1, n1 = run_sgg_loader(a, rank, world, dev, u8=u8)
+                ld, s1, n1 = run_sgg_loader(sub, rank, world, dev, u8=u8)
                 s1.opt.unfuse()
                 return pick(ld)
 
 
             def isd():
                 # configs[2]: fewer steps (a step is ~10x longer), its own roofline block
-                res, s2, n2 = run_instance_styled(a, rank, world, dev, steps=max(4, a.steps // 4), warmup=2)
+                res, s2, n2 = run_instance_styled(sub, rank, world, dev, steps=max(4, a.steps // 4), warmup=2)
                 return res
 
             def eval_loops():
@@ -1032,7 +1130,7 @@ def main():
         line, step, net = run_res50(a, rank, world, dev)
         keep += [step, net]
 
-    if rank == 0 and world == 1 and not a.no_cpu_baseline and a.config == "sgg":
+    if rank == 0 and world == 1 and a.full and not a.no_cpu_baseline and a.config == "sgg":
         # the GPU box grants a CPU share (16 cores per GPU), not the whole host: never oversubscribe
         cores = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
         threads = min(16, cores)
@@ -1050,6 +1148,8 @@ def main():
                                 "stages_sample": "the oracle stage by stage on ONE 600x1000 frame / 32 ROIs, same protocol; "
                                                  "instance_styled_dg_step_1+1_frames = the configs[2] D+G step (fwd, bwd, SGD) on 1 "
                                                  "source + 1 target frame, 1 warm-up + 2 timed; vrd_head_fwd_bwd 1 + 3 (frames_per_s counts both frames)"}
+    if rank == 0 and a.dump_outputs:
+        write_outputs(a.dump_outputs)
     if rank == 0:
         print(json.dumps(line), flush=True)
     if torch.distributed.is_available() and torch.distributed.is_initialized():

@@ -3,6 +3,21 @@ to tests/golden/roi_align_fwd.npz -- outputs of the reference's own ``ROIAlignFo
 "extracted", oracle/build_ref.py) -- and to the transpose of that pinned forward for the backward."""
 import numpy as np
 
+# (B, C, H, W, ah, aw, scale): shapes roi_align_fwd.npz does not hold, incl. non-square grids and another scale
+FRESH_SHAPES = ((1, 3, 7, 5, 8, 8, 1 / 16.0), (3, 16, 25, 40, 8, 8, 1 / 16.0), (2, 8, 14, 14, 15, 15, 1 / 16.0),
+                (2, 5, 20, 30, 3, 9, 1 / 8.0), (1, 2, 38, 63, 2, 2, 1 / 16.0))
+
+
+def fresh_roi_align_inputs():
+    """The seeded (feat, rois, ah, aw, scale) cases of tests/golden/roi_align_fwd_fresh.npz (tools/gen_golden.py
+    gen_roi_align_fresh), in order: one generator draws every map and every ROI seed."""
+    from i2vsgg_amd import synthetic as syn
+    rng = np.random.default_rng(77)
+    for (B, C, H, W, ah, aw, scale) in FRESH_SHAPES:
+        feat = rng.standard_normal((B, C, H, W), dtype=np.float32)
+        rois = syn.roi_cases(int(rng.integers(1 << 20)), B, H, W, scale=1.0 / scale)
+        yield feat, rois, ah, aw, scale
+
 
 def _sha(a):
     import hashlib

@@ -406,7 +406,7 @@ def test_joint_step_full_size_on_one_gpu(fresh_cfg):
     import argparse
     import bench
     fresh_cfg("res101", bench.SET_CFGS[6:])
-    a = argparse.Namespace(layers=101, no_graph=False, warmup=1, steps=3)
+    a = argparse.Namespace(layers=101, no_graph=False, warmup=1, steps=3, full=True, dump_outputs="")     # --full: the roofline block
     line, (dstep, sstep), (det, sgg) = bench.run_joint(a, 0, 1, torch.device(DEV))
     try:
         cfgd = line["config"]
@@ -428,6 +428,35 @@ def test_joint_step_full_size_on_one_gpu(fresh_cfg):
         assert torch.equal(frozen, sgg.RCNN_base[6][22].conv3.weight.detach())      # the relation net's trunk is frozen (:148)
     finally:
         sstep.opt.unfuse()
+
+
+def test_bench_plain_headline_run_and_its_outputs(fresh_cfg, tmp_path):
+    """bench.py's plain run of the headline (configs[1]) as main() drives it: the timed steps and the line -- no roofline block --
+    and --dump-outputs: the loss, the backbone's feature maps and a fixed sample of every trained head parameter, as the last
+    timed step left them, in float32, within 64 MB."""
+    import argparse
+    import os
+    import bench
+    fresh_cfg("res101", bench.SET_CFGS[6:])
+    bench._OUTPUTS.clear()
+    a = argparse.Namespace(layers=101, no_graph=False, warmup=1, steps=3, full=False, dump_outputs=str(tmp_path))
+    line, step, net = bench.run_sgg(a, 0, 1, torch.device(DEV))
+    try:
+        assert line["steps"] == 3 and line["unit"] == "frames/s" and line["higher_is_better"] is True and line["dtype"] == "f32"
+        assert line["value"] > 0 and abs(line["value"] * line["ms_per_step"] / 1e3 - 2.0) < 1e-6      # 2 frames per timed step
+        assert "roofline" not in line and line["config"]["hip_graph"], line["config"]["graph_error"]
+        bench.write_outputs(str(tmp_path))
+        got = {f[:-len(".npy")]: np.load(os.path.join(tmp_path, f)) for f in os.listdir(tmp_path)}
+        assert set(got) == {"loss", "fmap"} | {n for n, _ in net.named_parameters() if n.startswith("vrd.")}
+        assert all(v.dtype == np.float32 for v in got.values()) and sum(v.nbytes for v in got.values()) <= 64 << 20
+        assert got["loss"].shape == (1,) and got["loss"][0] == float(step.loss) and np.isfinite(got["loss"][0])
+        assert got["fmap"].shape == (2, 1024, 38, 63)
+        np.testing.assert_array_equal(got["fmap"], step.fmap.cpu().numpy())
+        np.testing.assert_array_equal(got["vrd.fc7.fc.bias"], net.vrd.fc7.fc.bias.detach().cpu().numpy())   # whole: below the cap
+        assert 600000 < got["vrd.fc6.fc.weight"].size <= 1 << 20                                       # a sample of 205M elements
+    finally:
+        step.opt.unfuse()
+        bench._OUTPUTS.clear()
 
 
 def test_sgg_step_full_size_vs_oracle(fresh_cfg):

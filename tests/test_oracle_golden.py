@@ -285,7 +285,8 @@ def test_avgpool_matches_torch():
 
 
 # ----------------------------------------------------------------------------- RoIAlign: pinned by the reference's own C
-from roi_align_pin import check_roi_align_against_golden, roi_align_matrix, roi_align_bwd_from_matrix  # noqa: E402
+from roi_align_pin import (check_roi_align_against_golden, fresh_roi_align_inputs, roi_align_matrix,  # noqa: E402
+                           roi_align_bwd_from_matrix)
 
 
 @pytest.mark.parametrize("C,H,W,B", syn.ROI_ALIGN_GOLDEN_CASES)
@@ -302,18 +303,20 @@ def test_roi_align_fwd_bit_equal_to_the_reference_c(gold, C, H, W, B):
                                    cops.roi_align_fwd(feat, rois, 7, 7, 1 / 16.0))
 
 
-def test_roi_align_fwd_vs_the_reference_library_on_fresh_shapes():
-    """Where oracle/_ref travelled (it is a built artefact: git-ignored, shipped to the GPU box): the restatement against
-    the reference's compiled function on shapes the fixture does not hold, incl. non-square grids and another scale."""
+def test_roi_align_fwd_vs_the_reference_library_on_fresh_shapes(gold):
+    """The restatement against the reference's compiled function on shapes roi_align_fwd.npz does not hold, incl. non-square
+    grids and another scale: the function's outputs are stored (tests/golden/roi_align_fwd_fresh.npz, tier "extracted",
+    tools/gen_golden.py gen_roi_align_fresh), and where oracle/_ref was built the library is also called live."""
     from oracle import build_ref
-    if not build_ref.available():
-        pytest.skip("oracle/_ref not built here (python -m oracle.build_ref needs /root/reference)")
-    rng = np.random.default_rng(77)
-    for (B, C, H, W, ah, aw, scale) in ((1, 3, 7, 5, 8, 8, 1 / 16.0), (3, 16, 25, 40, 8, 8, 1 / 16.0), (2, 8, 14, 14, 15, 15, 1 / 16.0),
-                                        (2, 5, 20, 30, 3, 9, 1 / 8.0), (1, 2, 38, 63, 2, 2, 1 / 16.0)):
-        feat = rng.standard_normal((B, C, H, W), dtype=np.float32)
-        rois = syn.roi_cases(int(rng.integers(1 << 20)), B, H, W, scale=1.0 / scale)
-        assert np.array_equal(cops.roi_align_fwd(feat, rois, ah, aw, scale), build_ref.roi_align_fwd(feat, rois, ah, aw, scale))
+    g = gold("roi_align_fwd_fresh")
+    assert str(g["tier"]) == "extracted"
+    live = build_ref.available()
+    for i, (feat, rois, ah, aw, scale) in enumerate(fresh_roi_align_inputs()):
+        assert np.array_equal(rois, g["s%d_rois" % i]) and feat.astype(np.float64).sum() == g["s%d_feat_sum" % i]
+        got = cops.roi_align_fwd(feat, rois, ah, aw, scale)
+        assert got.dtype == np.float32 and np.array_equal(got, g["s%d_out" % i]), i
+        if live:
+            assert np.array_equal(got, build_ref.roi_align_fwd(feat, rois, ah, aw, scale)), i
 
 
 @pytest.mark.parametrize("B,C,H,W", [(2, 5, 9, 11), (1, 3, 19, 32)])

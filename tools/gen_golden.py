@@ -133,6 +133,24 @@ def gen_roi_align():
     save("roi_align_fwd", "extracted", **out)
 
 
+def gen_roi_align_fresh():
+    """``ROIAlignForwardCpu`` (oracle/build_ref.py, as gen_roi_align) on the shapes of tests/roi_align_pin.py FRESH_SHAPES --
+    non-square grids and another scale, which roi_align_fwd.npz does not hold: the ROIs and the full outputs (~95k floats)."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from oracle import build_ref
+    from roi_align_pin import fresh_roi_align_inputs
+    build_ref.build()
+    out = {}
+    for i, (feat, rois, ah, aw, scale) in enumerate(fresh_roi_align_inputs()):
+        ref = build_ref.roi_align_fwd(feat, rois, ah, aw, scale)
+        out["s%d_rois" % i] = rois
+        out["s%d_feat_sum" % i] = np.array(feat.astype(np.float64).sum())
+        out["s%d_out" % i] = ref
+        same = np.array_equal(ref, cops.roi_align_fwd(feat, rois, ah, aw, scale))
+        print("   %s %dx%d scale %g: oracle restatement bit-equal: %s" % (feat.shape, ah, aw, scale, same))
+    save("roi_align_fwd_fresh", "extracted", **out)
+
+
 # ----------------------------------------------------------------------------- the two eval tails (SURVEY.md 8f rows f1 / f3)
 def gen_eval_tails():
     """f1: the per-image detection loop of test_net_instance_styleD_bilinear.py:151-221 driven with the reference's own
@@ -689,13 +707,17 @@ def main():
     ap.add_argument("--only", default="")
     a = ap.parse_args()
     os.makedirs(GOLD, exist_ok=True)
-    todo = a.only.split(",") if a.only else ["direct", "roialign", "tails", "rpn", "nets", "full", "ctx", "step", "vrd"]
+    todo = a.only.split(",") if a.only else ["direct", "roialign", "roialign_fresh", "tails", "rpn", "nets", "full", "ctx", "step",
+                                             "vrd"]
     if "direct" in todo:
         print("[direct imports]")
         gen_direct()
     if "roialign" in todo:
         print("[RoIAlign forward: the reference's C function compiled from its own lines]")
         gen_roi_align()
+    if "roialign_fresh" in todo:
+        print("[RoIAlign forward on further shapes: the same compiled function]")
+        gen_roi_align_fresh()
     if "tails" in todo:
         print("[eval tails: direct imports + detection_output compiled from its own lines]")
         gen_eval_tails()

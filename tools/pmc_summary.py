@@ -72,7 +72,7 @@ def block(kernel):
 
 
 summary = {
-    "command": "rocprofv3 --pmc FETCH_SIZE | --pmc WRITE_SIZE (separate passes) -- python3 bench.py --steps K --warmup W --no-cpu-baseline --no-also --no-graph",
+    "command": "rocprofv3 --pmc FETCH_SIZE | --pmc WRITE_SIZE (separate passes) -- python3 bench.py --full --steps K --warmup W --no-cpu-baseline --no-also --no-graph",
     "steps_in_run": steps,
     "note": "FETCH_SIZE/WRITE_SIZE are KB. gfx950 correction (MI355X_MICROARCH.md, HBM): FETCH_SIZE reports 1/2 of wide coalesced streaming reads -> doubled.",
     "conv_gemm_f32": block("conv_gemm_f32"),

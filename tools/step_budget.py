@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Per-step budget of the REPLAYED step graph from one `rocprofv3 --kernel-trace` csv of `bench.py --no-also --no-cpu-baseline`
+"""Per-step budget of the REPLAYED step graph from one `rocprofv3 --kernel-trace` csv of `bench.py --full --no-also --no-cpu-baseline`
 (the timed form: one HIP graph per step, head of batch k beside the backbone branches of batch k+1).
 
 One steady-state period = the window between two launches of an anchor kernel that occurs once per step.  Kernels are put
