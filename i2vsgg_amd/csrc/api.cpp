@@ -24,6 +24,7 @@ int g_i2v_tuning[I2V_TUNE_COUNT] = {
     /* CONV_GEMM */ 1, /* STAGGER */ 0, /* ROIALIGN_COLS */ 2, /* WGRAD_PER_CU */ 4, /* WGRAD_XCD */ 1,
     /* FC_FOLD */ 0, /* GEMM_X3 */ 0, /* GEMM_PERSIST */ 0, /* WGRAD_PRIO */ 0, /* STREAM_TILE */ 1,
     /* KGROUPS */ 0, /* WGRAD_ORDERED_GFLOP */ 1000000, /* GEMM_DMA */ 1, /* WGRAD_DMA */ 1, /* ROIALIGN_BWD */ 1, /* NMS_SCAN */ 2,
+    /* FC_UPDATE */ 1,
 };
 
 extern "C" int32_t i2v_build_flags(void) {

@@ -2338,7 +2338,190 @@ wgrad_reduce_scalar_kernel(const float* __restrict__ part, float* __restrict__ g
         gw[e] = v;
     }
 }
+// ---------------------------------------------------------------- fused update of a linear layer (round 7)
+// i2v_conv_wgrad_sgd on a linear / pointwise problem (1x1 filter, stride 1, no padding: x is [M][K], gy [M][N], W and its
+// momentum [N][K]) of at most 256 rows: the relation head's fc6 (4096 x 50176) and fc7 (4096 x 4096) at M = 128.  The tiled
+// fused kernel (conv_wgrad2_f32<4, 2, true>) ran fc6 as 25 088 workgroups of four K-stages each: every one re-fetched its
+// 64 KB gy strip and 32 KB x tile, paid its own W / m prefetch and LDS epilogue, and overlapped HBM with MFMA only by chance
+// (0.845 ms = 3.9 TB/s of the 3.29 GB it must move).  Here one 8-wave workgroup per CU stays:
+//  - it owns 128 filters (16 per wave) and a contiguous range of 64-tap tiles; the workgroups of one tap range are dealt to
+//    one XCD (the 32 filter strips of fc6 = the 32 CUs of an XCD), so an x tile comes from HBM once and from that L2 32 times;
+//  - its gy^T strip lives in registers for the whole launch (a wave's 16 filters x M rows = M / 4 VGPRs);
+//  - per tile: the x tile goes global -> registers -> LDS (double-buffered, loaded one tile ahead), the W / m tiles of tile
+//    t + 2 are loaded (16-byte non-temporal buffer loads) while tile t + 1 computes, W' / m' leave as 16-byte non-temporal stores.
+// Bit-equal to conv_wgrad2_f32 (any tile form): every output has one accumulator chain of v_mfma_f32_16x16x4_f32 over the
+// same four-row sets {32 st + 16 s2 + 4 k + t : k = 0..3}, in the same (st, s2, t) order, A = the gy side, B = the x side,
+// zero rows past M on both sides, the same number of 32-row stages, and the same SGD expression.  Only the column a tap takes
+// inside a 16x16 block differs (MFMA column c of block j = tap 4 c + j), which no output's arithmetic sees: a lane's four
+// accumulators then hold four CONSECUTIVE taps of one filter row, so the epilogue moves float4s without an LDS transpose.
+constexpr int FCU_WAVES = 8, FCU_THREADS = 64 * FCU_WAVES, FCU_BN = 16 * FCU_WAVES, FCU_TK = 64;
+struct FcuP {
+    const float* x; const float* gy; float* w; float* m;
+    float lr, mom, wd;
+    int M, N, K;
+    int strips, chunks, tiles, groups;       // filter strips x tap chunks = groups workgroups with work; tiles = 64-tap tiles of K
+    unsigned x_bytes, gy_bytes, w_bytes;     // each < 2 GiB: a masked offset carries the 2 GiB bit (the buffer returns zeros / drops the store)
+};
+
+template <int NS>       // NS 32-row stages (ceil(M / 32), as many as the tiled kernel runs): a constant, so that no branch in
+__global__ void __launch_bounds__(FCU_THREADS) fc_update_f32(const FcuP p) {     // the loop muddles the compiler's vmcnt accounting
+    // the launch is padded to a multiple of 8; XCD g (= blockIdx.x % 8 under round-robin dispatch) takes the contiguous range
+    // [g G / 8, (g + 1) G / 8) of the chunk-major work order, as conv_wgrad2_f32's xcd_remap
+    const int L = (int)blockIdx.x, g = L & 7, r = L >> 3;
+    const int start = (int)(((long long)g * p.groups) >> 3), count = (int)(((long long)(g + 1) * p.groups) >> 3) - start;
+    if (r >= count) return;
+    const int idx = start + r, chunk = idx / p.strips, strip = idx - chunk * p.strips;
+    const int t0 = (int)((long long)chunk * p.tiles / p.chunks), t1 = (int)((long long)(chunk + 1) * p.tiles / p.chunks);
+
+    constexpr unsigned MASK = 0x80000000u, NT = 2;      // NT: the cache-policy bit of a non-temporal buffer access
+    constexpr int ROWS = 32 * NS;
+    __shared__ __attribute__((aligned(16))) float xs[2][ROWS * FCU_TK];     // x tile, [row][tap]: the fragment reads are conflict-free as it stands
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, fr = lane & 15, fg = lane >> 4;
+    const int n0 = strip * FCU_BN;
+    const __amdgpu_buffer_rsrc_t gr = __builtin_amdgcn_make_buffer_rsrc((void*)p.gy, 0, p.gy_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc((void*)p.x, 0, p.x_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t wr = __builtin_amdgcn_make_buffer_rsrc((void*)p.w, 0, p.w_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t mr = __builtin_amdgcn_make_buffer_rsrc((void*)p.m, 0, p.w_bytes, 0x00020000);
+
+    // A fragments of the whole reduction: lane (fr, fg) holds gy[32 st + 16 s2 + 4 fg + t][n0 + 16 wave + fr], q = 4 s2 + t
+    float a[NS * 8];
+    {
+        const unsigned na = (unsigned)(n0 + 16 * wave + fr);
+        const bool nin = (int)na < p.N;
+#pragma unroll
+        for (int st = 0; st < NS; ++st)
+#pragma unroll
+            for (int q = 0; q < 8; ++q) {
+                const unsigned row = (unsigned)(32 * st + 16 * (q >> 2) + 4 * fg + (q & 3));
+                const unsigned off = ((row * (unsigned)p.N + na) * 4u) | ((nin && (int)row < p.M) ? 0u : MASK);
+                a[st * 8 + q] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(gr, off, 0, 0));
+            }
+    }
+
+    // x staging: thread = (rows tid / 16 + 32 q, taps 4 (tid % 16) ..); rows past M and taps past K read as zeros (the B side of
+    // a zero row must be 0, not whatever the LDS held: 0 * NaN is NaN)
+    float4 xv[NS];
+    auto xload = [&](int t) {                            // t >= t1: nothing to stage, the masked loads move no bytes
+        const unsigned k = (unsigned)(t * FCU_TK + 4 * (tid & 15));
+        const bool kin = t < t1 && (int)k < p.K;
+#pragma unroll
+        for (int q = 0; q < NS; ++q) {
+            const unsigned row = (unsigned)((tid >> 4) + 32 * q);
+            const unsigned off = ((row * (unsigned)p.K + k) * 4u) | ((kin && (int)row < p.M) ? 0u : MASK);
+            xv[q] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(xr, off, 0, 0));
+        }
+    };
+    auto xstore = [&](int buf) {
+#pragma unroll
+        for (int q = 0; q < NS; ++q) *(float4*)&xs[buf][((tid >> 4) + 32 * q) * FCU_TK + 4 * (tid & 15)] = xv[q];
+    };
+    // W / m of a tile: lane (fr, fg), q = 0..3 -> filter n0 + 16 wave + 4 fg + q, taps t * 64 + 4 fr ..  (K % 4 == 0)
+    auto wm_offsets = [&](int t, unsigned (&off)[4]) {
+        const unsigned k = (unsigned)(t * FCU_TK + 4 * fr);
+        const bool kin = t < t1 && (int)k < p.K;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const unsigned n = (unsigned)(n0 + 16 * wave + 4 * fg + q);
+            off[q] = ((n * (unsigned)p.K + k) * 4u) | ((kin && (int)n < p.N) ? 0u : MASK);
+        }
+    };
+    auto wm_load = [&](int t, float4 (&wv)[4], float4 (&mv)[4]) {
+        unsigned off[4];
+        wm_offsets(t, off);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            wv[q] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(wr, off[q], 0, NT));
+            mv[q] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(mr, off[q], 0, NT));
+        }
+    };
+
+    int buf = 0;
+    auto body = [&](int t, float4 (&wv)[4], float4 (&mv)[4]) {
+        f32x4 acc[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int st = 0; st < NS; ++st) {
+            float4 b[8];                                 // B fragments of a stage: a ds_read_b128 per lane feeds four MFMAs
+#pragma unroll
+            for (int q = 0; q < 8; ++q) b[q] = *(const float4*)&xs[buf][(32 * st + 16 * (q >> 2) + 4 * fg + (q & 3)) * FCU_TK + 4 * fr];
+#pragma unroll
+            for (int q = 0; q < 8; ++q) {
+                acc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[st * 8 + q], b[q].x, acc[0], 0, 0, 0);
+                acc[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[st * 8 + q], b[q].y, acc[1], 0, 0, 0);
+                acc[2] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[st * 8 + q], b[q].z, acc[2], 0, 0, 0);
+                acc[3] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[st * 8 + q], b[q].w, acc[3], 0, 0, 0);
+            }
+        }
+        __builtin_amdgcn_sched_barrier(0);               // the update's arithmetic stays behind the MFMAs: hoisted, it waits for W / m there
+        unsigned off[4];
+        wm_offsets(t, off);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {                    // g' = g + wd*p ; m = mom*m + g' ; p -= lr*m   (same order as sgd_momentum_kernel)
+            float4 pv = wv[q], m4 = mv[q];
+            m4.x = p.mom * m4.x + (acc[0][q] + p.wd * pv.x); m4.y = p.mom * m4.y + (acc[1][q] + p.wd * pv.y);
+            m4.z = p.mom * m4.z + (acc[2][q] + p.wd * pv.z); m4.w = p.mom * m4.w + (acc[3][q] + p.wd * pv.w);
+            pv.x -= p.lr * m4.x; pv.y -= p.lr * m4.y; pv.z -= p.lr * m4.z; pv.w -= p.lr * m4.w;
+            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, m4), mr, off[q], 0, NT);
+            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, pv), wr, off[q], 0, NT);
+        }
+        xstore(buf ^ 1);                                 // x of tile t + 1, loaded a tile ago (the other buffer is free since the last barrier)
+        xload(t + 2);
+        wm_load(t + 2, wv, mv);                          // the registers just consumed, two tiles ahead
+        __syncthreads();
+        buf ^= 1;
+    };
+
+    float4 wA[4], mA[4], wB[4], mB[4];
+    xload(t0);
+    // the A fragments and the first x tile: the one drain of the launch.  Without it the compiler, unsure across the loop's back
+    // edge how many loads are younger than the A fragments, waits with vmcnt(0) in front of every tile's first MFMA
+    __builtin_amdgcn_s_waitcnt(0);
+    xstore(0);
+    xload(t0 + 1);
+    wm_load(t0, wA, mA);
+    wm_load(t0 + 1, wB, mB);
+    __syncthreads();
+    // unrolled by two: each register set is reloaded in place, never copied.  Both ways back to the top pass through both
+    // bodies (an odd last tile leaves the loop), so the compiler counts the same loads in flight on each
+    for (int t = t0;; t += 2) {
+        body(t, wA, mA);
+        if (t + 1 >= t1) break;
+        body(t + 1, wB, mB);
+        if (t + 2 >= t1) break;
+    }
+}
 }  // namespace
+
+// the persistent fused update (fc_update_f32); false: a shape it does not cover, which takes launch_wgrad's tiled kernel --
+// filters of more than one tap, more than 256 rows, Cout % 4 != 0 or the first-generation wgrad selected (their MFMA chain
+// differs: bit-equality holds against conv_wgrad2_f32 only), operands of 2 GiB or more
+static bool launch_fc_update(const WgP& p, hipStream_t st) {
+    if (!g_i2v_tuning[I2V_TUNE_FC_UPDATE] || !g_wgrad_v2) return false;
+    const bool lin = p.KH == 1 && p.KW == 1 && p.pad == 0 && p.stride == 1;
+    const long long xb = (long long)p.M * p.K * 4, gb = (long long)p.M * p.N * 4, wb = (long long)p.N * p.K * 4;
+    if (!lin || p.M > 256 || p.N % 4 || p.K % 4 || xb >= (1ll << 31) || gb >= (1ll << 31) || wb >= (1ll << 31)) return false;
+    FcuP q = {};
+    q.x = p.x; q.gy = p.gy; q.w = p.gw; q.m = p.sgd_m; q.lr = p.lr; q.mom = p.mom; q.wd = p.wd;
+    q.M = p.M; q.N = p.N; q.K = p.K;
+    q.strips = i2v_cdiv(p.N, FCU_BN);
+    q.tiles = i2v_cdiv(p.K, FCU_TK);
+    q.chunks = std::min(std::max(NUM_CU / q.strips, 1), q.tiles);      // one workgroup per CU
+    q.groups = q.strips * q.chunks;
+    q.x_bytes = (unsigned)xb; q.gy_bytes = (unsigned)gb; q.w_bytes = (unsigned)wb;
+    const unsigned grid = (unsigned)((q.groups + 7) / 8 * 8);
+    switch (i2v_cdiv(p.M, 32)) {
+    case 1: fc_update_f32<1><<<grid, FCU_THREADS, 0, st>>>(q); break;
+    case 2: fc_update_f32<2><<<grid, FCU_THREADS, 0, st>>>(q); break;
+    case 3: fc_update_f32<3><<<grid, FCU_THREADS, 0, st>>>(q); break;
+    case 4: fc_update_f32<4><<<grid, FCU_THREADS, 0, st>>>(q); break;
+    case 5: fc_update_f32<5><<<grid, FCU_THREADS, 0, st>>>(q); break;
+    case 6: fc_update_f32<6><<<grid, FCU_THREADS, 0, st>>>(q); break;
+    case 7: fc_update_f32<7><<<grid, FCU_THREADS, 0, st>>>(q); break;
+    default: fc_update_f32<8><<<grid, FCU_THREADS, 0, st>>>(q); break;
+    }
+    return true;
+}
 
 // picks the kernel + pixel split for one wgrad problem; returns false when v2 cannot be used
 constexpr int kWgradOrderedMax = 16;     // most splits the ordered finish of a filter gradient sums (one workgroup reads them all)
@@ -2795,7 +2978,7 @@ extern "C" int32_t i2v_conv_wgrad_sgd(const float* x, const float* gy, float* w,
         i2v_set_error("conv_wgrad_sgd: shape needs a split over pixels; use i2v_conv_wgrad + i2v_sgd_momentum");
         return I2V_ERR_UNSUPPORTED;
     }
-    launch_wgrad(p, 0.f, true, (hipStream_t)stream);
+    if (!launch_fc_update(p, (hipStream_t)stream)) launch_wgrad(p, 0.f, true, (hipStream_t)stream);
     I2V_CHECK_LAUNCH("conv_wgrad_sgd");
     return I2V_OK;
 }
