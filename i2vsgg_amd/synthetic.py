@@ -268,6 +268,29 @@ def roi_cases(seed, B, H, W, scale=16.0, n=24):
     return r
 
 
+def sampled_rois(seed, B, H, W, R, n_gt=8, scale=16.0, with_gt=False):
+    """(B*R,5) ROIs [b,x1,y1,x2,y2] shaped like the proposal target layer's output for a (B,C,H,W) map: per frame at most
+    round(0.25 R) foreground ROIs, each a jittered copy (every corner moved by at most 6 % of the box's side: IoU >= 0.6) of
+    one of n_gt <= 8 gt boxes, so that they pile up in clusters as the sampler's do; the rest background boxes drawn over the
+    whole frame.  ``with_gt``: also the (B,n_gt,4) gt boxes the foreground was drawn around."""
+    rng = np.random.default_rng(seed)
+    im_h, im_w = H * scale, W * scale
+    n_fg = min(int(round(0.25 * R)), R)
+    out = np.zeros((B * R, 5), np.float32)
+    gts = np.zeros((B, min(n_gt, 8), 4), np.float32)
+    for b in range(B):
+        gts[b] = gt = boxes(int(rng.integers(1 << 30)), min(n_gt, 8), im_h, im_w, 48, min(im_h, im_w) * 0.6).astype(np.float64)
+        src = gt[rng.integers(0, gt.shape[0], n_fg)]
+        side = np.concatenate([src[:, 2:] - src[:, :2]] * 2, 1)
+        fg = np.clip(src + rng.uniform(-0.06, 0.06, src.shape) * side, 0, [im_w - 1, im_h - 1, im_w - 1, im_h - 1])
+        bg = boxes(int(rng.integers(1 << 30)), R - n_fg, im_h, im_w, 16, min(im_h, im_w) * 0.8)
+        r = out[b * R:(b + 1) * R]
+        r[:, 0] = b
+        r[:n_fg, 1:] = fg
+        r[n_fg:, 1:] = bg
+    return (out, gts) if with_gt else out
+
+
 ROI_ALIGN_GOLDEN_CASES = ((4, 9, 11, 2), (64, 19, 32, 2), (1024, 38, 63, 1))          # (C, H, W, B)
 
 

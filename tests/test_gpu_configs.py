@@ -41,7 +41,18 @@ def _finite(d):
 
 
 def test_instance_styled_step_full_size(fresh_cfg):
-    """configs[2] at full size, B = 4 + 4 frames of 600x1000, ResNet-101, 32 ROI / frame:
+    _step_full_size(fresh_cfg, 32)
+
+
+def test_instance_styled_step_full_size_at_128_rois(fresh_cfg):
+    """The same at the yml's own TRAIN.BATCH_SIZE = RPN_POST_NMS_TOP_N_TARGET = 128: 512 ROIs (25 088 pooled rows) per branch,
+    keep buffers of (4, 128) with up to 32 foreground rows per frame.  The plain form is handed the fused form's proposals
+    (see _step_full_size)."""
+    _step_full_size(fresh_cfg, 128)
+
+
+def _step_full_size(fresh_cfg, R):
+    """configs[2] at full size, B = 4 + 4 frames of 600x1000, ResNet-101, R ROI / frame:
       * every loss of the step is finite and the trained parameters of every group move (layer1-3, layer4, RPN, both
         discriminators, the detection heads);
       * the step on the fused kernels (one-kernel netD_pixel, Winograd forward / data gradient for the trained 3x3 layers,
@@ -50,19 +61,36 @@ def test_instance_styled_step_full_size(fresh_cfg):
         direct 3x3 kernels, torch.optim.SGD with the reference's parameter groups) for two consecutive steps -- the second
         one sees the first one's update -- within 1e-3 relative, same np.random stream;
       * the captured form (device-side target sampling, ONE HIP graph) replays to finite losses close to the host-sampled
-        ones and keeps training."""
-    cfg = fresh_cfg("res101", ["TRAIN.BATCH_SIZE", "32", "TRAIN.RPN_POST_NMS_TOP_N_TARGET", "32"])
+        ones and keeps training.
+    At R = 128 the plain form's RPN hands on the fused form's proposals of the same step (its own RPN losses still count).
+    The two backbones differ in the last bits (Winograd against direct 3x3 kernels: 1e-5 against 1e-6 per layer), which
+    moves proposal corners by ~1e-4 px and lets a score near-tie swap a box.  At 4 x 128 sampled rows such a swapped box is
+    sampled: at step 0, 503 of 504 distinct sampled boxes agree, and the one that differs moves RCNN_loss_cls by 7.9e-5 and
+    every gradient behind the ROIs by ~2e-3.  After the update, 443 of 505 agree and RCNN_loss_cls differs by 6.4e-3.  That is
+    sampling, not arithmetic, so the forms are compared on equal proposals."""
+    cfg = fresh_cfg("res101", ["TRAIN.BATCH_SIZE", str(R), "TRAIN.RPN_POST_NMS_TOP_N_TARGET", str(R)])
     from i2vsgg_amd import ops, train
     names = ["RCNN_base.4.0.conv1.weight", "RCNN_base.6.22.conv2.weight", "RCNN_top.0.2.conv3.weight",
              "RCNN_rpn.RPN_Conv.weight", "netD_pixel.conv1.weight", "netD_style.fc_1.weight", "RCNN_cls_score.weight",
              "RCNN_bbox_pred.bias"]
 
-    def run(plain):
+    def run(plain, proposals=None):
         torch.manual_seed(0)
         np.random.seed(cfg.RNG_SEED)
         net = train.build_instance_styled_net(101, device=DEV)
         before = {k: v.detach().clone() for k, v in net.named_parameters() if k in names}
         step = train.InstanceStyleDStep(net, 4, seed=3, device=DEV)
+        seen = []
+        if R != 32:                          # record the proposals (fused form) or hand on the recorded ones (plain form)
+            rpn_forward = net.RCNN_rpn.forward
+
+            def spy(*a, **k):
+                out = rpn_forward(*a, **k)
+                if proposals is not None:
+                    out = (proposals[len(seen)],) + tuple(out[1:])
+                seen.append(out[0].detach().clone())
+                return out
+            net.RCNN_rpn.forward = spy
         saved = (ops.WINOGRAD_TRAIN, net.netD_pixel.forward, ops.BLOCK_FUSED)      # WINOGRAD_TRAIN off: direct wgrad too
         if plain:
             ops.WINOGRAD_TRAIN = False
@@ -88,14 +116,20 @@ def test_instance_styled_step_full_size(fresh_cfg):
             moved = {k: float((dict(net.named_parameters())[k].detach() - before[k]).abs().max()) for k in names}
         finally:
             ops.WINOGRAD_TRAIN, net.netD_pixel.forward, ops.BLOCK_FUSED = saved
-        return out, moved, net, step
+            if R != 32:
+                del net.RCNN_rpn.forward
+        return out, moved, net, step, seen
 
-    fused, moved, net, step = run(False)
+    fused, moved, net, step, proposals = run(False)
     assert all(_finite(d) for d in fused), fused
     assert all(v > 0 for v in moved.values()), moved
-    plain, _, net2, step2 = run(True)
+    plain, _, net2, step2, _ = run(True, proposals if R != 32 else None)
     del net2, step2
-    for a, b in zip(fused, plain):
+    tag = "step_full_size" + ("" if R == 32 else "[R=%d]" % R)
+    for i, (a, b) in enumerate(zip(fused, plain)):
+        if R != 32:
+            record_margin(tag, "fused vs plain, equal proposals, step %d: max rel. loss diff" % i,
+                          max(abs(a[k] - b[k]) / max(abs(b[k]), 1e-6) for k in a), 1e-3)
         for k in a:
             assert abs(a[k] - b[k]) <= 1e-3 * max(abs(b[k]), 1e-6), (k, fused, plain)
     # ---- captured form (device-side sampling, ONE graph) against the host form AT EQUAL SAMPLES (round-3 review: the 25 % band
@@ -117,14 +151,15 @@ def test_instance_styled_step_full_size(fresh_cfg):
     assert not torch.equal(w0, net.RCNN_base[6][22].conv2.weight.detach())
     # what the device samplers drew is a legal draw of the reference's rules (anchor_target_layer.py:123-143,
     # proposal_target_layer_cascade.py:140-182): <= 128 fg and exactly RPN_BATCHSIZE labelled anchors per frame (there are far
-    # more than 256 candidates at this size), 32 rois per frame of which <= round(0.25 * 32) foreground, every kept fg roi above
-    # FG_THRESH and every kept bg roi below it
+    # more than 256 candidates at this size), R rois per frame of which <= round(FG_FRACTION * R) foreground, every kept fg roi
+    # above FG_THRESH and every kept bg roi below it
     lab = drawn_a["labels"]
     assert lab.shape[0] == 4 and bool(((lab == 1).sum(1) <= 128).all()) and bool(((lab >= 0).sum(1) == cfg.TRAIN.RPN_BATCHSIZE).all())
     keep, nfg, mo = drawn_p["keep"], drawn_p["nfg"], drawn_p["max_ov"]
-    assert tuple(keep.shape) == (4, 32) and bool((nfg <= 8).all()) and bool((nfg >= 1).all())
+    n_fg = int(round(cfg.TRAIN.FG_FRACTION * R))
+    assert tuple(keep.shape) == (4, R) and bool((nfg <= n_fg).all()) and bool((nfg >= 1).all())
     kept_ov = torch.gather(mo, 1, keep)
-    slot = torch.arange(32, device=DEV).view(1, 32)
+    slot = torch.arange(R, device=DEV).view(1, R)
     assert bool((kept_ov[slot < nfg] >= cfg.TRAIN.FG_THRESH).all()) and bool((kept_ov[slot >= nfg] < cfg.TRAIN.BG_THRESH_HI).all())
     step._restore(saved)
     atl.sample_record = ptl.sample_record = None
@@ -137,6 +172,9 @@ def test_instance_styled_step_full_size(fresh_cfg):
     finally:
         atl.sample_replay = ptl.sample_replay = None
     assert len(want) == 10 and set(want) == set(got)
+    if R != 32:
+        record_margin(tag, "captured vs eager at equal samples: max rel. loss diff",
+                      max(abs(got[k] - want[k]) / max(abs(want[k]), 1e-6) for k in want), 1e-3)
     for k in want:
         assert abs(got[k] - want[k]) <= 1e-3 * max(abs(want[k]), 1e-6), (k, got, want)
     assert abs(got["det"] - (got["rpn_cls"] + got["rpn_box"] + got["rcnn_cls"] + got["rcnn_box"])) <= 1e-5 * got["det"]
@@ -147,13 +185,107 @@ def test_instance_styled_step_full_size(fresh_cfg):
     step.opt.unfuse()
 
 
+def test_instance_styled_step_full_size_is_bit_reproducible_at_128_rois(fresh_cfg):
+    """The captured two-branch step at full size and the yml's own 128 ROIs per frame (4 + 4 frames of 600x1000, ResNet-101,
+    512 ROIs per branch), run twice from equal weights on the same minibatch: the same bits in every loss of every step and in
+    every trained tensor, and no reduction that was asked to be ordered fell back to atomics.  The split counts of the filter
+    gradients here (netD_pixel's at 25 088 rows, layer4's at 8192) are not the ones of the small-frame test in test_gpu_models."""
+    cfg = fresh_cfg("res101")
+    assert cfg.TRAIN.BATCH_SIZE == 128 and cfg.TRAIN.RPN_POST_NMS_TOP_N_TARGET == 128
+    from i2vsgg_amd import train
+    from i2vsgg_amd._lib import lib
+
+    def run():
+        torch.manual_seed(0)
+        np.random.seed(cfg.RNG_SEED)
+        net = train.build_instance_styled_net(101, device=DEV)
+        step = train.InstanceStyleDStep(net, 4, seed=3, device=DEV)
+        assert step.branches
+        lib.i2v_ordered_fallbacks(1)
+        assert step.capture(warmup=1, restore=True), step.graph_error
+        losses = []
+        for _ in range(3):
+            step()
+            losses.append(step._loss_buf.clone())
+        torch.cuda.synchronize()
+        assert lib.i2v_ordered_fallbacks(1) == 0, "a reduction that was asked to be ordered ran on atomics"
+        w = {k: v.detach().clone() for k, v in net.named_parameters() if v.requires_grad}
+        step.opt.unfuse()
+        return torch.stack(losses), w
+
+    la, wa = run()
+    lb, wb = run()
+    assert bool(torch.isfinite(la).all()), la
+    assert torch.equal(la, lb), (la - lb).abs().max(dim=0).values.tolist()
+    assert float(la[0, 0]) != float(la[2, 0])                # the weights do move
+    diff = [k for k in wa if not torch.equal(wa[k], wb[k])]
+    assert not diff, (diff[:8], len(diff))
+
+
+def test_instance_styled_consistency_terms_at_128_rois_full_size(fresh_cfg):
+    """--cr at full size and the yml's 128 ROIs per frame, the one size at which the reference's hard-coded ``repeat(1,128)``
+    (trainval_net_instance_styleD_bilinear.py:300-311) and consistency_terms' actual ROI count agree: the step's
+    source_adv_cst / target_adv_cst against the reference's literal expression evaluated in float64 on the step's own
+    discriminator outputs (caught as the step's forward returns them).  Both bodies: the one-pass eager step
+    (train.consistency_terms) and the two-branch body a captured step records (train._consistency_term), run on eager launches
+    so that the outputs can be caught."""
+    cfg = fresh_cfg("res101")
+    assert cfg.TRAIN.BATCH_SIZE == 128 and cfg.TRAIN.RPN_POST_NMS_TOP_N_TARGET == 128
+    from i2vsgg_amd import train
+    torch.manual_seed(0)
+    np.random.seed(cfg.RNG_SEED)
+    net = train.build_instance_styled_net(101, device=DEV)
+    step = train.InstanceStyleDStep(net, 4, seed=3, device=DEV, cr=True)
+    assert step.branches
+    seen = {}
+    forward_features = net.forward_features
+
+    def spy(*a, **k):
+        out = forward_features(*a, **k)
+        target = a[5] if len(a) > 5 else k["target"]
+        d_inst, d_style = out if target else out[8:10]
+        seen[bool(target)] = (d_inst.detach().clone(), d_style.detach().clone())
+        return out
+    net.forward_features = spy
+    consistency_loss = torch.nn.MSELoss()
+    try:
+        for body, run in (("one pass", step), ("two branches", step._body_branches)):
+            seen.clear()
+            run()
+            torch.cuda.synchronize()
+            got = {k: float(v) for k, v in step.losses.items()}
+            assert set(seen) == {False, True}, body
+            for name, (out_d_instance, out_d_style) in (("source_adv_cst", seen[False]), ("target_adv_cst", seen[True])):
+                assert tuple(out_d_instance.shape) == (4 * 128, 1, 7, 7) and tuple(out_d_style.shape) == (4, 1)
+                out_d_instance_consist = torch.mean(out_d_instance.double(), dim=3)
+                out_d_instance_consist = torch.mean(out_d_instance_consist, dim=2)
+                consistency_prob = out_d_style.double().repeat(1, 128).view(-1, 1)
+                want = float(consistency_loss(out_d_instance_consist, consistency_prob.detach()))
+                err = abs(got[name] - want) / abs(want)
+                record_margin("consistency_terms_at_128_rois_full_size", "%s, %s rel. error vs float64" % (body, name), err, 1e-5)
+                assert err <= 1e-5, (body, name, got[name], want)
+    finally:
+        del net.forward_features
+    step.opt.unfuse()
+
+
 def test_instance_styled_target_half_full_size_vs_oracle(fresh_cfg):
+    _target_half_full_size_vs_oracle(fresh_cfg, 32)
+
+
+def test_instance_styled_target_half_full_size_vs_oracle_at_128_rois(fresh_cfg):
+    """The same at the yml's own RPN_POST_NMS_TOP_N_TARGET = 128 (config.py:51): 12000 -> 128 proposals, 128 pooled ROIs."""
+    _target_half_full_size_vs_oracle(fresh_cfg, 128)
+
+
+def _target_half_full_size_vs_oracle(fresh_cfg, R):
     """configs[2], the TARGET half at full size against the CPU oracle (round-3 review: the oracle comparison of this config
     existed only at 320x480 / ResNet-50): one 600x1000 frame through ResNet-101 C4 -> netD_style -> RPN head -> proposal layer
-    (12000 -> 32, NMS 0.7) -> RoIAlignAvg -> netD_pixel, no backward (trainval_net_instance_styleD_bilinear.py:293-296 reads
+    (12000 -> R, NMS 0.7) -> RoIAlignAvg -> netD_pixel, no backward (trainval_net_instance_styleD_bilinear.py:293-296 reads
     exactly these two outputs).  Same seeded weights; dloss_t and dloss_t_style within 1e-3 relative, the instance map
     element-wise, the proposals as a set (score near-ties between two conv implementations may swap neighbours)."""
-    cfg = fresh_cfg("res101", ["TRAIN.BATCH_SIZE", "32", "TRAIN.RPN_POST_NMS_TOP_N_TARGET", "32"])
+    fresh_cfg("res101", ["TRAIN.BATCH_SIZE", str(R), "TRAIN.RPN_POST_NMS_TOP_N_TARGET", str(R)])
+    tag = "target_half_full_size_vs_oracle" + ("" if R == 32 else "[R=%d]" % R)
     from i2vsgg_amd.model.faster_rcnn.layers import load_reference_state
     from i2vsgg_amd.model.faster_rcnn.resnet_instance_styleD_bilinear import resnet
     from oracle import cops, nets, rpn
@@ -181,17 +313,17 @@ def test_instance_styled_target_half_full_size_vs_oracle(fresh_cfg):
         d_inst_t, d_sty_t = net(torch.from_numpy(im).to(DEV), torch.from_numpy(info).to(DEV), torch.zeros(1, 1, 5, device=DEV),
                                 torch.zeros(1, device=DEV), target=True, eta=0.1, eta_style=0.001)
     rois = stash["rois"]
-    assert rois.shape == (1, 32, 5)
+    assert rois.shape == (1, R, 5)
     po = {k: v.clone() for k, v in p.items()}
     with torch.no_grad():
         feat, feat1 = nets.extract_feature(torch.from_numpy(im), po, blocks=(3, 4, 23))
         assert tuple(feat.shape) == (1, 1024, 38, 63) and tuple(feat1.shape) == (1, 512, 75, 125)
         d_sty_o = nets.netd_style(feat1, po, 0.001)
         cls, prob, box = nets.rpn_head(feat, po)
-    rois_o, _ = rpn.proposal_layer(prob[:, 9:].numpy(), box.numpy(), info, 12000, 32, 0.7)
+    rois_o, _ = rpn.proposal_layer(prob[:, 9:].numpy(), box.numpy(), info, 12000, R, 0.7)
     a = {tuple(np.round(x, 1)) for x in rois[0] if x[1:].any()}
     o = {tuple(np.round(x, 1)) for x in rois_o[0] if x[1:].any()}
-    record_margin("target_half_full_size_vs_oracle", "proposal set overlap (of %d)" % len(o), len(a & o) / len(o), TARGET_SET_OVERLAP)
+    record_margin(tag, "proposal set overlap (of %d)" % len(o), len(a & o) / len(o), TARGET_SET_OVERLAP)
     assert len(a & o) >= TARGET_SET_OVERLAP * len(o), (len(a & o), len(o))
     pooled = torch.from_numpy(cops.roi_align_avg_fwd(feat.numpy(), rois.reshape(-1, 5), 7, 7, 1.0 / 16.0))      # the HIP path's own rois
     with torch.no_grad():
@@ -199,6 +331,10 @@ def test_instance_styled_target_half_full_size_vs_oracle(fresh_cfg):
     rel = lambda x, y: abs(float(x) - float(y)) / max(abs(float(y)), 1e-12)
     got_t, want_t = 0.5 * torch.mean((1 - d_inst_t) ** 2).item(), 0.5 * torch.mean((1 - d_inst_o) ** 2).item()
     got_s, want_s = 0.5 * torch.mean((1 - d_sty_t) ** 2).item(), 0.5 * torch.mean((1 - d_sty_o) ** 2).item()
+    if R != 32:
+        record_margin(tag, "dloss_t rel. error", rel(got_t, want_t), 1e-3)
+        record_margin(tag, "dloss_t_style rel. error", rel(got_s, want_s), 1e-3)
+        assert d_inst_t.shape[0] == R
     assert rel(got_t, want_t) < 1e-3 and rel(got_s, want_s) < 1e-3, (got_t, want_t, got_s, want_s)
     np.testing.assert_allclose(d_inst_t.cpu().numpy(), d_inst_o.numpy(), rtol=1e-3, atol=1e-6)
     np.testing.assert_allclose(d_sty_t.cpu().numpy(), d_sty_o.numpy(), rtol=1e-3, atol=1e-7)
@@ -260,6 +396,38 @@ def test_device_sampling_statistics(fresh_cfg):
         z = (cnt[cand] - T * pr) / (T * pr * (1 - pr)) ** 0.5
         assert abs(float(cnt[cand].sum()) - T * k) < 0.5
         assert 0.7 < float((z * z).mean()) < 1.4 and float(z.abs().max()) < 5.0, (n, float((z * z).mean()), float(z.abs().max()))
+
+
+def test_device_sampling_statistics_at_128_rois(fresh_cfg):
+    """The device-side proposal sampler at the yml's own TRAIN.BATCH_SIZE = 128 (cfgs/res101.yml:12): keep buffers of (B, 128),
+    round(FG_FRACTION * 128) = 32 foreground rows where both classes exist, all 128 from the one class an image has, every kept
+    index of its class, and over many draws every candidate kept as often as the reference's rules make it: foreground without
+    replacement (Binomial(T, 32 / n) per candidate), background with replacement (Binomial(96 T, 1 / n))."""
+    cfg = fresh_cfg("res101")
+    from i2vsgg_amd.model.rpn.proposal_target_layer_cascade import _ProposalTargetLayer
+    R = cfg.TRAIN.BATCH_SIZE
+    fg_per = int(round(cfg.TRAIN.FG_FRACTION * R))
+    assert (R, fg_per) == (128, 32)
+    torch.manual_seed(1)
+    mo = torch.zeros(3, 400, device=DEV)
+    mo[0, :200] = 0.8; mo[0, 200:] = 0.2               # both classes
+    mo[1, :] = 0.9                                     # only fg
+    mo[2, :] = 0.1                                     # only bg
+    keep, nfg = _ProposalTargetLayer._sample_device(mo, R, fg_per)
+    assert tuple(keep.shape) == (3, R) and nfg.view(-1).tolist() == [32, 128, 0]
+    k0 = keep[0].tolist()
+    assert all(i < 200 for i in k0[:32]) and len(set(k0[:32])) == 32 and all(i >= 200 for i in k0[32:])
+    assert all(0 <= i < 400 for i in keep[1].tolist() + keep[2].tolist())
+    assert len(set(keep[1].tolist())) > 64 and len(set(keep[2].tolist())) > 64                      # spread over the candidates
+    T = 300
+    cnt = torch.zeros(400, device=DEV)
+    for _ in range(T):
+        kp, _n = _ProposalTargetLayer._sample_device(mo[:1], R, fg_per)
+        cnt += torch.bincount(kp[0].long(), minlength=400).float()
+    for cand, k, draws, pr in ((slice(0, 200), 32, T, 32 / 200), (slice(200, 400), 96, 96 * T, 1 / 200)):
+        z = (cnt[cand] - draws * pr) / (draws * pr * (1 - pr)) ** 0.5
+        assert abs(float(cnt[cand].sum()) - T * k) < 0.5
+        assert 0.7 < float((z * z).mean()) < 1.4 and float(z.abs().max()) < 5.0, (k, float((z * z).mean()), float(z.abs().max()))
 
 
 def test_res50_yml_full_frame_plumbing(fresh_cfg):

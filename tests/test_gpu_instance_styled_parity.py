@@ -31,15 +31,27 @@ from conftest import record_margin  # noqa: E402
 
 
 def test_instance_styled_source_and_target_losses_vs_oracle():
+    _source_and_target_losses_vs_oracle(32)
+
+
+def test_instance_styled_source_and_target_losses_vs_oracle_at_128_rois():
+    """The same at the yml's own TRAIN.BATCH_SIZE = RPN_POST_NMS_TOP_N_TARGET = 128 (cfgs/res101.yml:12, config.py:51): 4x the
+    sampled rows through RoIAlignAvg, netD_pixel, layer4 and the heads; and the 128 target proposals as a set against the
+    oracle's."""
+    _source_and_target_losses_vs_oracle(128)
+
+
+def _source_and_target_losses_vs_oracle(R):
     if not torch.cuda.is_available():
         pytest.fail("GPU tests need a GPU")
+    tag = "source_and_target_losses_vs_oracle" + ("" if R == 32 else "[R=%d]" % R)
     from i2vsgg_amd.model.faster_rcnn.layers import load_reference_state
     from i2vsgg_amd.model.faster_rcnn.resnet_instance_styleD_bilinear import resnet
     from i2vsgg_amd.model.utils import config as c
     from oracle import cops, nets, rpn
     c.cfg_from_file(c.default_cfg_file("res101"))
     c.cfg_from_list(["ANCHOR_SCALES", "[8, 16, 32]", "ANCHOR_RATIOS", "[0.5,1,2]", "MAX_NUM_GT_BOXES", "30",
-                     "TRAIN.BATCH_SIZE", "32", "TRAIN.RPN_POST_NMS_TOP_N_TARGET", "32"])
+                     "TRAIN.BATCH_SIZE", str(R), "TRAIN.RPN_POST_NMS_TOP_N_TARGET", str(R)])
     cfg = c.cfg
     try:
         B, H, W, n_cls = 2, 320, 480, 16
@@ -86,8 +98,16 @@ def test_instance_styled_source_and_target_losses_vs_oracle():
         for b in range(B):
             a = {tuple(np.round(x, 1)) for x in src_rois[b] if x[1:].any()}
             o = {tuple(np.round(x, 1)) for x in rois_o[b] if x[1:].any()}
-            record_margin("source_and_target_losses_vs_oracle", "proposal set overlap, frame %d (of %d)" % (b, len(o)), len(a & o) / len(o), min_overlap(len(o)) / len(o))
+            record_margin(tag, "proposal set overlap, frame %d (of %d)" % (b, len(o)), len(a & o) / len(o), min_overlap(len(o)) / len(o))
             assert len(a & o) >= min_overlap(len(o)), (len(a & o), len(o))
+        if R != 32:         # the 32-row target sets are compared at full size (test_gpu_configs.py); here the 128-row ones
+            assert tgt_rois.shape == (B, R, 5)
+            tgt_o, _ = rpn.proposal_layer(prob[:, 9:].numpy(), box.numpy(), info, 12000, R, 0.7)
+            for b in range(B):
+                a = {tuple(np.round(x, 1)) for x in tgt_rois[b] if x[1:].any()}
+                o = {tuple(np.round(x, 1)) for x in tgt_o[b] if x[1:].any()}
+                record_margin(tag, "target proposal set overlap, frame %d (of %d)" % (b, len(o)), len(a & o) / len(o), min_overlap(len(o)) / len(o))
+                assert len(a & o) >= min_overlap(len(o)), (len(a & o), len(o))
         rs = np.random.RandomState(3)
         L, T, IW, OW = rpn.anchor_target_layer(fh, fw, gt, info, rs)
         pair = cls.view(B, 2, 9 * fh, fw).permute(0, 2, 3, 1).reshape(-1, 2)
@@ -96,7 +116,7 @@ def test_instance_styled_source_and_target_losses_vs_oracle():
         o_rpn_cls = F.cross_entropy(pair[keep], lab[keep].long()).item()
         o_rpn_box = rpn.smooth_l1(box.numpy(), T, IW, OW, sigma=3, sum_dims=(1, 2, 3))
         # downstream of the proposals: feed the HIP path's own proposals so that the sampled set is identical
-        rois_b, labels_o, tg, inw, outw = rpn.proposal_target_layer(src_rois, gt, rs, batch_size=32)
+        rois_b, labels_o, tg, inw, outw = rpn.proposal_target_layer(src_rois, gt, rs, batch_size=R)
         assert np.array_equal(rois_b, rois.cpu().numpy()) and np.array_equal(labels_o.reshape(-1), labels.cpu().numpy())
         pooled = torch.from_numpy(cops.roi_align_avg_fwd(feat.numpy(), rois_b.reshape(-1, 5), 7, 7, 1.0 / 16.0))
         with torch.no_grad():
@@ -127,7 +147,10 @@ def test_instance_styled_source_and_target_losses_vs_oracle():
             "dloss_t_style": (0.5 * torch.mean((1 - d_sty_t) ** 2).item(), 0.5 * torch.mean((1 - d_sty_o) ** 2).item()),
         }
         for name, (got, ref) in checks.items():
+            if R != 32:
+                record_margin(tag, name + " rel. error", rel(got, ref), REL)
             assert rel(got, ref) < REL, (name, got, ref)
+        assert d_inst.shape[0] == B * R
         np.testing.assert_allclose(d_inst.detach().cpu().numpy(), d_inst_o.numpy(), rtol=REL, atol=1e-6)
     finally:
         cfg.TRAIN.BATCH_SIZE = 128

@@ -197,7 +197,7 @@ def test_anchor_target_layer_vs_reference_golden(cfg, gold, B):
     np.testing.assert_allclose(out[1].cpu().numpy(), g["B%d_targets" % B], rtol=1e-4, atol=1e-5)
 
 
-@pytest.mark.parametrize("B,R", [(1, 128), (2, 32)])
+@pytest.mark.parametrize("B,R", [(1, 128), (2, 32), (4, 128)])
 def test_proposal_target_layer_vs_reference_golden(cfg, gold, B, R):
     from i2vsgg_amd.model.rpn.proposal_target_layer_cascade import _ProposalTargetLayer
     g = gold("proposal_target")

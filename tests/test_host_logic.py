@@ -521,3 +521,26 @@ def test_stage_pipeline_bookkeeping_trains_every_minibatch_once():
         assert not st.bubble
         st()
     assert st.trained[-3:] == [7, 7, 7]
+
+
+@pytest.mark.parametrize("B,R", [(4, 128), (8, 128), (4, 32)])
+def test_sampled_rois_are_shaped_like_the_samplers_output(B, R):
+    """synthetic.sampled_rois, the ROI set of the 128-ROI kernel tests: R rows per frame in frame order, the first
+    round(0.25 R) clustered on the frame's gt boxes at IoU >= 0.5 (the proposal target layer's FG_THRESH), all inside the
+    frame, valid corners."""
+    from i2vsgg_amd import synthetic as syn
+    from oracle import rpn
+    H, W = 38, 63
+    rois, gt = syn.sampled_rois(5, B, H, W, R, with_gt=True)
+    assert rois.shape == (B * R, 5) and rois.dtype == np.float32 and gt.shape == (B, 8, 4)
+    n_fg = int(round(0.25 * R))
+    for b in range(B):
+        r = rois[b * R:(b + 1) * R]
+        assert np.all(r[:, 0] == b)
+        assert np.all(r[:, 1:3] >= 0) and np.all(r[:, 3] <= W * 16 - 1) and np.all(r[:, 4] <= H * 16 - 1)
+        assert np.all(r[:, 3] > r[:, 1]) and np.all(r[:, 4] > r[:, 2])
+        best = rpn.iou_matrix(r[:, 1:].astype(np.float32), gt[b]).max(1)
+        assert np.all(best[:n_fg] >= 0.5), best[:n_fg].min()
+        assert len({int(i) for i in rpn.iou_matrix(r[:n_fg, 1:], gt[b]).argmax(1)}) >= 4      # several clusters, not one
+    assert not np.array_equal(syn.sampled_rois(5, B, H, W, R), syn.sampled_rois(6, B, H, W, R))
+    assert np.array_equal(syn.sampled_rois(5, B, H, W, R), rois)

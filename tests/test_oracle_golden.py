@@ -71,7 +71,8 @@ def test_proposal_layer(gold, B):
     g = gold("proposal_layer")
     fg, deltas = _rpn_inputs(200 + B, B)
     info = np.array([[600, 1000, 1.0]] * B, np.float32)
-    for mode, pre, post in (("train", 12000, 2000), ("test", 6000, 300), ("target", 12000, 32)):
+    for mode, pre, post in (("train", 12000, 2000), ("test", 6000, 300), ("target", 12000, 32),
+                            ("target128", 12000, 128)):
         rois, _ = rpn.proposal_layer(fg, deltas, info, pre, post, 0.7)
         ref = g["rois_B%d_%s" % (B, mode)]
         assert rois.shape == ref.shape
@@ -92,7 +93,7 @@ def test_anchor_target_layer(gold, B):
     np.testing.assert_allclose(T, g["B%d_targets" % B], rtol=1e-5, atol=1e-6)
 
 
-@pytest.mark.parametrize("B,R", [(1, 128), (2, 32)])
+@pytest.mark.parametrize("B,R", [(1, 128), (2, 32), (4, 128)])
 def test_proposal_target_layer(gold, B, R):
     g = gold("proposal_target")
     gt, _ = syn.gt_boxes(400 + B, B, 8)

@@ -333,7 +333,7 @@ def gen_rpn_layers(cfg):
         prob, deltas = _rpn_inputs(200 + B, B)
         info = np.array([[600, 1000, 1.0], [600, 1000, 1.0]], np.float32)[:B]
         for mode, key, target, post in (("train", "TRAIN", False, None), ("test", "TEST", False, None),
-                                        ("target", "TRAIN", True, 32)):
+                                        ("target", "TRAIN", True, 32), ("target128", "TRAIN", True, 128)):
             if post is not None:
                 cfg.TRAIN.RPN_POST_NMS_TOP_N_TARGET = post
             rois = layer((torch.from_numpy(prob), torch.from_numpy(deltas), torch.from_numpy(info), key),
@@ -356,7 +356,7 @@ def gen_rpn_layers(cfg):
 
     ptl = _ProposalTargetLayer(16)
     out = {}
-    for B, R in ((1, 128), (2, 32)):
+    for B, R in ((1, 128), (2, 32), (4, 128)):         # (4, 128): one branch of the yml's own step (TRAIN.BATCH_SIZE: 128)
         cfg.TRAIN.BATCH_SIZE = R
         gt, nb = syn.gt_boxes(400 + B, B, 8)
         rois = np.zeros((B, 2000, 5), np.float32)
