@@ -86,6 +86,10 @@ SIGNATURES = {
     "i2v_dstyle_fused_fwd": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _l, _i, _i, _i, _i, _p, _z, _p]),
     "i2v_relation_topk_workspace_bytes": (_z, [_i, _i]),
     "i2v_relation_topk": (_i, [_p, _p, _p, _p, _i, _i, _i, _p, _p, _p, _p, _z, _p]),
+    "i2v_video_associate_workspace_bytes": (_z, [_i, _i, _i]),
+    "i2v_video_associate": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _z, _p]),
+    "i2v_video_viou_match_workspace_bytes": (_z, [_i, _i]),
+    "i2v_video_viou_match": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _l, _i, _i, C.c_double, _p, _p, _p, _p, _z, _p]),
     "i2v_image_prep_size": (_i, [_i, _i, _i, _p, _p, _p]),
     "i2v_image_prep": (_i, [_p, _i, _i, _i, _i, _p, _i, _p, _i, _i, _p]),
     "i2v_det_postprocess_workspace_bytes": (_z, [_i, _i]),

@@ -1344,6 +1344,72 @@ def relation_topk(rel_score, conf, ixs, ixo, k=100):
     return pair, pred, out
 
 
+def _to_dev(x, dtype, device):
+    return torch.as_tensor(x).to(device=device, dtype=dtype).contiguous()
+
+
+def _video_status(ws, what):
+    bad = int(ws[:4].view(torch.int32).item())              # the caller reads the results next anyway
+    if bad:
+        raise _lib.I2VError("%s: the offset tables are out of range at entry %d" % (what, bad - 1))
+
+
+def video_associate(frame_off, frame_no, pred_off, score, triplet, boxes, device=None):
+    """Frame-to-video association of a packed batch of videos in one launch (include/i2vsgg_hip.h, i2v_video_associate;
+    ``video.pack_frames`` builds the arrays).  Arrays or tensors: frame_off (V+1), frame_no (F), pred_off (F+1) int32,
+    score (P) fp64, triplet (P,3) int32, boxes (P,8) fp64.  Returns device tensors (rel_id (P) int32, rel_start (P) int32,
+    rel_len (P) int32, rel_score (P) fp64, n_rel (V) int32)."""
+    dev = torch.device(device if device is not None else "cuda")
+    if dev.type != "cuda":
+        raise _lib.I2VError("i2vsgg_amd ops run on the GPU only (got device %s); video.associate(device=None) is the host form" % dev)
+    counts = np.diff(np.asarray(torch.as_tensor(pred_off).cpu()))
+    max_per_frame = int(counts.max()) if len(counts) else 0
+    frame_off, frame_no, pred_off = (_to_dev(x, torch.int32, dev) for x in (frame_off, frame_no, pred_off))
+    score, boxes, triplet = _to_dev(score, torch.float64, dev), _to_dev(boxes, torch.float64, dev), _to_dev(triplet, torch.int32, dev)
+    V, F, P = frame_off.numel() - 1, frame_no.numel(), score.numel()
+    if pred_off.numel() != F + 1 or triplet.numel() != 3 * P or boxes.numel() != 8 * P:
+        raise ValueError("video_associate: array sizes do not agree")
+    rel_id, rel_start, rel_len = (torch.zeros((P,), device=dev, dtype=torch.int32) for _ in range(3))
+    rel_score = torch.zeros((P,), device=dev, dtype=torch.float64)
+    n_rel = torch.zeros((max(V, 0),), device=dev, dtype=torch.int32)
+    with torch.cuda.device(dev):
+        ws = workspace(lib.i2v_video_associate_workspace_bytes(V, F, P), dev, "video")
+        check(lib.i2v_video_associate(ptr(frame_off), ptr(frame_no), ptr(pred_off), ptr(score), ptr(triplet), ptr(boxes), V, F, P,
+                                      max_per_frame, ptr(rel_id), ptr(rel_start), ptr(rel_len), ptr(rel_score), ptr(n_rel),
+                                      ptr(ws), ws.numel(), stream()), "video_associate")
+        if V > 0:
+            _video_status(ws, "video_associate")
+    return rel_id, rel_start, rel_len, rel_score, n_rel
+
+
+def video_viou_match(pred_off, pred_rel, pred_score, gt_off, gt_rel, boxes, viou_threshold=0.5, device=None):
+    """Trajectory overlaps and the detection metric's greedy matching for a packed batch of videos
+    (include/i2vsgg_hip.h, i2v_video_viou_match; ``video.pack_eval`` builds the arrays).  Returns device tensors (ov
+    (n_pred, max_gt) fp64, hit (n_pred) int32, hit_ov (n_pred) fp64)."""
+    dev = torch.device(device if device is not None else "cuda")
+    if dev.type != "cuda":
+        raise _lib.I2VError("i2vsgg_amd ops run on the GPU only (got device %s); video.match(device=None) is the host form" % dev)
+    pc, gc = (np.diff(np.asarray(torch.as_tensor(x).cpu())) for x in (pred_off, gt_off))
+    max_pred, max_gt = (int(c.max()) if len(c) else 0 for c in (pc, gc))
+    pred_off, gt_off = _to_dev(pred_off, torch.int32, dev), _to_dev(gt_off, torch.int32, dev)
+    pred_rel, gt_rel = _to_dev(pred_rel, torch.int32, dev), _to_dev(gt_rel, torch.int32, dev)
+    pred_score, boxes = _to_dev(pred_score, torch.float64, dev), _to_dev(boxes, torch.float64, dev)
+    V, NP, NG, NB = pred_off.numel() - 1, pred_score.numel(), gt_rel.numel() // 10, boxes.numel() // 4
+    if gt_off.numel() != V + 1 or pred_rel.numel() != 10 * NP or gt_rel.numel() != 10 * NG or boxes.numel() != 4 * NB:
+        raise ValueError("video_viou_match: array sizes do not agree")
+    ov = torch.full((NP, max_gt), -1.0, device=dev, dtype=torch.float64)
+    hit = torch.full((NP,), -1, device=dev, dtype=torch.int32)
+    hit_ov = torch.full((NP,), -1.0, device=dev, dtype=torch.float64)
+    with torch.cuda.device(dev):
+        ws = workspace(lib.i2v_video_viou_match_workspace_bytes(NP, NG), dev, "video")
+        check(lib.i2v_video_viou_match(ptr(pred_off), ptr(pred_rel), ptr(pred_score), ptr(gt_off), ptr(gt_rel), ptr(boxes), V, NP,
+                                       NG, NB, max_pred, max_gt, float(viou_threshold), ptr(ov), ptr(hit), ptr(hit_ov),
+                                       ptr(ws), ws.numel(), stream()), "video_viou_match")
+        if V > 0 and NP > 0:
+            _video_status(ws, "video_viou_match")
+    return ov, hit, hit_ov
+
+
 class _L2NormRowsFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, eps):

@@ -329,3 +329,127 @@ def context_inputs(B=2, H=320, W=480):
         jit = np.random.default_rng(440 + b).normal(0, 6, (48, 4)).astype(np.float32)
         rois[b, :48, 1:] = np.clip(gt[b, np.arange(48) % 6, :4] + jit, 0, [W - 1, H - 1, W - 1, H - 1])
     return im, info, gt, nb, rois
+
+
+# ----------------------------------------------------------------------------------------------------------------
+# videos for the association / evaluation of i2vsgg_amd.video (tests/golden/video_*.npz hold the reference's results)
+# ----------------------------------------------------------------------------------------------------------------
+def video_frames(seed, n_frames, n_objects=7, n_pred=100, integer=False, quant=0, p_break=0.02, first_frame=0, n_cand=120):
+    """One video's per-frame relation predictions, [[fno, [[conf, [s, p, o], [sub_box, obj_box], rel_idex], ...]], ...], as
+    the relation test loop would hand them over: a few persistent objects whose boxes drift slowly (object 1 is a twin of
+    object 0: same class, nearly the same box, the same scores -- true ties, and two predictions that want one relation),
+    ``n_cand`` (subject, predicate, object) candidates whose scores move slowly (triangle waves plus a little noise), the best ``n_pred`` of
+    them per frame, listed in a shuffled order.  With probability ``p_break`` per frame an object jumps, which ends its
+    relations.  Only uniform draws and + - * are used, so every machine regenerates the same bits.  ``integer``: boxes
+    with integer coordinates; ``quant``: scores rounded to multiples of 1/quant (exact sums, many ties)."""
+    rng = np.random.RandomState(seed)
+    cls = rng.randint(1, 16, n_objects)
+    cls[1] = cls[0]
+
+    def draw_box():
+        w, h = rng.randint(60, 200), rng.randint(60, 200)
+        x, y = rng.randint(0, 640 - w), rng.randint(0, 360 - h)
+        b = np.array([x, y, x + w, y + h], np.float64)
+        return b if integer else b + rng.random_sample(4)
+
+    box = np.stack([draw_box() for _ in range(n_objects)])
+    pairs = [(i, j) for i in range(n_objects) for j in range(n_objects) if i != j and not (i < 2 and j < 2)]
+    cand = []
+    while len(cand) < n_cand:
+        i, j = pairs[rng.randint(len(pairs))]
+        if i == 1:
+            continue                                     # the twin's candidates are copies of object 0's, below
+        c = (i, j, int(rng.randint(1, 62)))
+        if c not in cand:
+            cand.append(c)
+    wave = [(rng.random_sample() * 0.6 + 0.2, rng.random_sample() * 0.15, int(rng.randint(40, 200)), int(rng.randint(200)))
+            for _ in cand]
+    twin = [k for k, c in enumerate(cand) if c[0] == 0][:12]
+    cand += [(1, cand[k][1], cand[k][2]) for k in twin]
+    wave += [wave[k] for k in twin]
+    frames = []
+    for t in range(n_frames):
+        if t:
+            step = rng.randint(-2, 3, (n_objects, 4)).astype(np.float64) if integer else rng.random_sample((n_objects, 4)) * 3 - 1.5
+            step[:, 2:] = step[:, :2] + (step[:, 2:] - step[:, :2]) * 0.25          # mostly a translation
+            if integer:
+                step = np.round(step)
+            box = box + step
+            for k in np.nonzero(rng.random_sample(n_objects) < p_break)[0]:
+                if k > 1:
+                    box[k] = draw_box()
+            box[1] = box[0] + (2.0 if integer else 2.25)
+        score = np.empty(len(cand))
+        noise = rng.random_sample(len(cand)) * 0.02      # no two stretches of a wave repeat the same numbers
+        noise[n_cand:] = noise[twin]
+        for k, (b, a, period, phase) in enumerate(wave):
+            u = ((t + phase) % period) / float(period)
+            score[k] = b + a * (4 * abs(u - 0.5) - 1) + noise[k]
+        if quant:
+            score = np.round(score * quant) / quant
+        best = np.argsort(-score, kind="stable")[:n_pred]
+        best = best[rng.permutation(len(best))]
+        frames.append([first_frame + t, [[float(score[k]), [float(cls[cand[k][0]]), float(cand[k][2]), float(cls[cand[k][1]])],
+                                          [box[cand[k][0]].tolist(), box[cand[k][1]].tolist()], int(k)] for k in best]])
+    return frames
+
+
+def video_fixture_cases():
+    """The videos of tests/golden/video_association.npz, {vid: frames}: a dozen of 30-150 frames, one long, and the edge
+    cases by construction (tools/gen_golden.py asserts that each is present before it writes the file)."""
+    out = {}
+    for k, (n, integer, quant) in enumerate([(30, False, 0), (48, True, 0), (64, False, 0), (80, True, 64), (96, False, 0),
+                                             (120, False, 64), (150, True, 0), (40, False, 0)]):
+        out["v%02d" % k] = video_frames(100 + k, n, integer=integer, quant=quant, first_frame=7 * k)
+    # empty frames: both ends, inside, a run of 11 (its middle stays empty), short runs near the ends, a gap in numbers
+    fr = video_frames(120, 90)
+    for i in [0, 1, 5, 6, 20, 30, 31, 32] + list(range(45, 56)) + [83, 84, 85, 88, 89]:
+        fr[i][1] = []
+    del fr[70:73]
+    out["empty"] = fr
+    # a frame with more than 100 predictions, in a video short enough that the window of an empty frame is clipped twice
+    fr = video_frames(121, 34, n_pred=130, n_cand=140)
+    fr[3][1] = []
+    fr[31][1] = []
+    out["wide"] = fr
+    # the object of a relation moves away while its subject stays; relations of exactly 9 and exactly 10 members
+    fr = video_frames(122, 60, p_break=0.0, integer=True)
+    sub, obj, far = [10.0, 10.0, 110.0, 110.0], [200.0, 50.0, 300.0, 150.0], [400.0, 200.0, 500.0, 300.0]
+    for t, f in enumerate(fr):
+        f[1].append([0.96875 if t < 25 else 0.9609375, [3.0, 60.0, 4.0], [list(sub), list(obj if t < 25 else far)], 900])
+        if 5 <= t < 14:
+            f[1].append([0.953125, [3.0, 59.0, 4.0], [list(sub), list(obj)], 901])
+        if 20 <= t < 30:
+            f[1].append([0.9375, [3.0, 58.0, 4.0], [list(sub), list(obj)], 902])
+    out["moved"] = fr
+    # many short relations: more than 200 survive the 10-member rule
+    out["many"] = video_frames(123, 260, p_break=0.03, n_objects=9)
+    fr = video_frames(125, 600, p_break=0.004)
+    for f in fr:                                         # one relation as long as the video
+        f[1].append([0.97265625, [5.0, 60.0, 6.0], [[20.5, 30.25, 140.0, 200.5], [300.0, 40.5, 420.25, 210.0]], 900])
+    out["long"] = fr
+    return out
+
+
+def video_groundtruth(relations, seed):
+    """Ground truth for ``video.evaluate`` made from one video's predicted relations: some are annotated with jittered
+    boxes (hits), some with a shifted duration (a partial overlap), some triplets are never predicted, and some
+    predictions have no annotation of their triplet."""
+    rng = np.random.RandomState(seed)
+    gts, seen = [], set()
+    for k, r in enumerate(relations):
+        key = (tuple(r["triplet"]), tuple(r["duration"]))
+        if k % 3 == 2 or key in seen:                    # not annotated; twins share one annotation
+            continue
+        seen.add(key)
+        n = len(r["sub_traj"])
+        shift = [0, 0, n // 3, (2 * n) // 3][k % 4]      # the annotation starts later: a partial overlap
+        jit = lambda traj: [[c + float(rng.randint(-3, 4)) for c in b] for b in traj[shift:]]
+        gts.append({"triplet": list(r["triplet"]), "duration": [r["duration"][0] + shift, r["duration"][1]],
+                    "sub_traj": jit(r["sub_traj"]), "obj_traj": jit(r["obj_traj"])})
+        if len(gts) >= 30:
+            break
+    for k in range(3):                                   # annotated, never predicted
+        b = [[10.0 * k, 20.0, 90.0 + 10 * k, 120.0]] * 12
+        gts.append({"triplet": [1, 61 - k, 2], "duration": [3, 15], "sub_traj": b, "obj_traj": b})
+    return gts

@@ -1,0 +1,446 @@
+"""Video level of the relation test loop: per-frame triplets -> video relation instances -> VidVRD metrics.
+
+``associate`` links the top triplets of consecutive frames into relation instances (triplet, duration, subject and object
+trajectory, score) and ``evaluate`` scores them against annotated relations: detection mAP, recall@50/100 and tagging
+precision@1/5/10 (lib/utils.py ``association`` / ``evaluate`` of the reference).
+
+What runs where.  Packing the nested lists into flat arrays, the fill of empty frames, the final "at least 10 members,
+best 200" selection and the gather of trajectories are host code (list logic on small data).  The frame loop of the
+association and the trajectory overlaps / matching of the detection metric are HIP kernels (csrc/video.hip) when a
+``device`` is given.  With ``device=None`` the same rules run as plain numpy on the host: evaluation scripts work on a
+machine without a GPU, and the kernels have something to be compared with.  Both paths share the packing, the selection
+and the gather, and both do their arithmetic in float64 in the same operation order, so they agree bit for bit.
+"""
+import numpy as np
+
+MAX_PER_FRAME = 100          # predictions of one frame that take part
+MAX_PER_VIDEO = 200          # relations kept per video
+MIN_MEMBERS = 10             # a relation seen on fewer frames is dropped
+FILL_WINDOW = 4              # an empty frame is filled unless every frame within this many positions is empty too
+REL_COLS = 10                # ops.video_viou_match relation row
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# host pre-pass
+# ------------------------------------------------------------------------------------------------------------------
+def fill_empty_frames(frames):
+    """``frames``: [[frame number, predictions], ...] of one video.  Returns a new list in ascending frame number (stable)
+    where an empty frame has taken the predictions of its nearest non-empty neighbour (the left one on equal distance),
+    unless every frame within 4 positions of it (itself included, the window clipped to the video) is empty too."""
+    frames = sorted(frames, key=lambda fr: int(fr[0]))
+    n = len(frames)
+    empty = [len(fr[1]) == 0 for fr in frames]
+    if all(empty):
+        return [[fr[0], fr[1]] for fr in frames]
+    left, right = [0] * n, [0] * n                   # distance to the nearest non-empty frame on either side, 0: none
+    last = -1
+    for i in range(n):
+        if not empty[i]:
+            last = i
+        elif last >= 0:
+            left[i] = i - last
+    last = -1
+    for i in range(n - 1, -1, -1):
+        if not empty[i]:
+            last = i
+        elif last >= 0:
+            right[i] = last - i
+    out = []
+    for i, fr in enumerate(frames):
+        preds = fr[1]
+        if empty[i]:
+            lo = max(0, i - FILL_WINDOW) if i >= FILL_WINDOW else 0
+            hi = min(n - 1, i + FILL_WINDOW)
+            if not all(empty[lo:hi + 1]):
+                src = i - left[i] if right[i] == 0 or (0 < left[i] <= right[i]) else i + right[i]
+                preds = frames[src][1]
+        out.append([fr[0], preds])
+    return out
+
+
+def from_frame_results(results, frame_to_video=None):
+    """What ``test_sgg_emb.py`` pickles -- {frame path: (rlp_labels, tuple_confs, sub_bboxes, obj_bboxes, rel_idex)}, five
+    Nones for a frame without pairs -- as ``frame_relations`` {vid: [[fno, [[conf, [s, p, o], [sub_box, obj_box],
+    rel_idex], ...]], ...]}.  ``frame_to_video`` maps a path to (vid, fno): a dict or a callable; None: one video "0",
+    frames numbered in the order of ``results``."""
+    out = {}
+    for k, (path, res) in enumerate(results.items()):
+        if frame_to_video is None:
+            vid, fno = "0", k
+        elif callable(frame_to_video):
+            vid, fno = frame_to_video(path)
+        else:
+            vid, fno = frame_to_video[path]
+        labels, confs, sub, obj, idx = res
+        preds = []
+        if isinstance(confs, np.ndarray):
+            labels, sub, obj = np.asarray(labels).tolist(), np.asarray(sub).tolist(), np.asarray(obj).tolist()
+            confs, idx = confs.tolist(), np.asarray(idx).tolist()
+            preds = [[confs[j], labels[j], [sub[j], obj[j]], idx[j]] for j in range(len(confs))]
+        out.setdefault(vid, []).append([fno, preds])
+    return out
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# association
+# ------------------------------------------------------------------------------------------------------------------
+class Packed(object):
+    """Flat arrays of a batch of videos (the layout of ``ops.video_associate``)."""
+
+    def __init__(self, vids, frame_off, frame_no, pred_off, score, triplet, boxes, rel_idex):
+        self.vids, self.frame_off, self.frame_no, self.pred_off = vids, frame_off, frame_no, pred_off
+        self.score, self.triplet, self.boxes, self.rel_idex = score, triplet, boxes, rel_idex
+
+
+def pack_frames(frame_relations):
+    """Sort the frames, fill the empty ones, order each frame's predictions by descending score (stable) and cut them to
+    the first 100.  Videos without a single prediction are left out, as the reference leaves them out of its result."""
+    vids, frame_off, frame_no, counts = [], [0], [], []
+    score, trip, boxes, idex = [], [], [], []
+    for vid, frames in frame_relations.items():
+        frames = fill_empty_frames(frames)
+        if not any(len(fr[1]) for fr in frames):
+            continue
+        vids.append(vid)
+        for fno, preds in frames:
+            if len(preds) > 1:
+                preds = sorted(preds, key=lambda p: p[0], reverse=True)[:MAX_PER_FRAME]
+            frame_no.append(int(fno))
+            counts.append(len(preds))
+            for p in preds:
+                score.append(p[0])
+                trip.append(p[1])
+                boxes.append(list(p[2][0]) + list(p[2][1]))
+                idex.append(p[3])
+        frame_off.append(len(frame_no))
+    pred_off = np.zeros(len(counts) + 1, np.int32)
+    np.cumsum(np.asarray(counts, np.int64), out=pred_off[1:])
+    rel_idex = np.empty(len(idex), object)
+    rel_idex[:] = idex
+    return Packed(vids, np.asarray(frame_off, np.int32), np.asarray(frame_no, np.int32), pred_off,
+                  np.asarray(score, np.float64).reshape(-1), np.asarray(trip, np.float64).astype(np.int32).reshape(-1, 3),
+                  np.asarray(boxes, np.float64).reshape(-1, 8), rel_idex)
+
+
+def _iou(a, b):
+    """IoU of box rows in the reference's operation order: no +1, 0 for an empty or touching intersection."""
+    left, right = np.maximum(a[:, 0], b[:, 0]), np.minimum(a[:, 2], b[:, 2])
+    up, down = np.maximum(a[:, 1], b[:, 1]), np.minimum(a[:, 3], b[:, 3])
+    s1 = (a[:, 2] - a[:, 0]) * (a[:, 3] - a[:, 1])
+    s2 = (b[:, 2] - b[:, 0]) * (b[:, 3] - b[:, 1])
+    sc = (down - up) * (right - left)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        iou = sc / (s1 + s2 - sc)
+    return np.where((left >= right) | (down <= up), 0.0, iou)
+
+
+def _note(stats, key, value):
+    if stats is not None and value < stats.get(key, np.inf):
+        stats[key] = float(value)
+
+
+def _gap_margin(stats, key, values, same):
+    """Smallest relative gap between neighbouring unequal values of a descending order; equal values must be true ties
+    (``same(i, j)``: built from the same numbers), else the margin is 0.  ``stats["exact_sums"]``: the caller knows that
+    every sum is exact (scores on a coarse binary grid), so equal values are equal in any summation order."""
+    if stats is None or len(values) < 2:
+        return
+    order = np.argsort(-values, kind="stable")
+    v = values[order]
+    gap = (v[:-1] - v[1:]) / np.maximum(np.maximum(np.abs(v[:-1]), np.abs(v[1:])), 1e-300)
+    for k in np.nonzero(gap == 0)[0]:
+        stats["ties_" + key] = stats.get("ties_" + key, 0) + 1
+        if not stats.get("exact_sums") and not same(order[k], order[k + 1]):
+            _note(stats, key, 0.0)
+    if (gap > 0).any():
+        _note(stats, key, gap[gap > 0].min())
+
+
+def associate_arrays_host(pk, stats=None):
+    """The rules of ``ops.video_associate`` in numpy, on the same arrays, with the same outputs.  ``stats`` (a dict)
+    collects the smallest relative margin of the decisions that rest on computed doubles: ``iou`` (an IoU against 0.5),
+    ``mean`` (two unequal means of open relations of one frame)."""
+    P = len(pk.score)
+    rel_id = np.zeros(P, np.int32)
+    rel_start, rel_len, rel_score = np.zeros(P, np.int32), np.zeros(P, np.int32), np.zeros(P, np.float64)
+    n_rel = np.zeros(len(pk.frame_off) - 1, np.int32)
+    for v in range(len(pk.frame_off) - 1):
+        f0, f1 = int(pk.frame_off[v]), int(pk.frame_off[v + 1])
+        base = int(pk.pred_off[f0])
+        span = int(pk.pred_off[f1]) - base
+        r_start, r_len, r_sum = np.zeros(span, np.int32), np.zeros(span, np.int32), np.zeros(span, np.float64)
+        nxt, prev_no = 0, None
+        o_id = np.zeros(0, np.int64)                 # the open relations, in the order the last frame touched them
+        o_trip, o_box = np.zeros((0, 3), np.int32), np.zeros((0, 8))
+        for f in range(f0, f1):
+            p0, p1 = int(pk.pred_off[f]), int(pk.pred_off[f + 1])
+            fno = int(pk.frame_no[f])
+            if prev_no is None or fno != prev_no + 1:
+                o_id = o_id[:0]
+            prev_no = fno
+            order = np.argsort(-pk.score[p0:p1], kind="stable")[:MAX_PER_FRAME]
+            S, T, B = pk.score[p0:p1][order], pk.triplet[p0:p1][order], pk.boxes[p0:p1][order]
+            n, m = len(S), len(o_id)
+            assign = np.full(n, -1, np.int64)
+            if n and m:
+                means = r_sum[o_id] / r_len[o_id]
+                _gap_margin(stats, "mean", means,
+                            lambda i, j: r_sum[o_id[i]] == r_sum[o_id[j]] and r_len[o_id[i]] == r_len[o_id[j]])
+                cand = np.argsort(-means, kind="stable")
+                pi, ci = np.nonzero((T[:, None, :] == o_trip[cand][None, :, :]).all(-1))
+                if len(pi):
+                    si, oi = _iou(o_box[cand[ci], :4], B[pi, :4]), _iou(o_box[cand[ci], 4:], B[pi, 4:])
+                    if stats is not None:
+                        _note(stats, "iou", min(np.abs(si - 0.5).min(), np.abs(oi - 0.5).min()) / 0.5)
+                    ok = (si >= 0.5) & (oi >= 0.5)
+                    compat = np.zeros((n, m), bool)
+                    compat[pi[ok], ci[ok]] = True
+                    if stats is not None:
+                        stats["contested"] = stats.get("contested", 0) + int((compat.sum(0) > 1).sum())
+                        stats["multi_candidate"] = stats.get("multi_candidate", 0) + int((compat.sum(1) > 1).sum())
+                    avail = np.ones(m, bool)
+                    for p in np.nonzero(compat.any(1))[0]:
+                        c = compat[p] & avail
+                        if c.any():
+                            r = int(c.argmax())
+                            avail[r] = False
+                            assign[p] = cand[r]
+            ids = np.empty(n, np.int64)
+            new = assign < 0
+            ids[~new] = o_id[assign[~new]]
+            ids[new] = nxt + np.arange(int(new.sum()))
+            nxt += int(new.sum())
+            r_start[ids[new]] = fno
+            r_sum[ids] = np.where(new, S, r_sum[ids] + S)        # ids of one frame are distinct
+            r_len[ids] += 1
+            rel_id[p0 + order] = ids
+            o_id, o_trip, o_box = ids, T, B
+        n_rel[v] = nxt
+        rel_start[base:base + nxt], rel_len[base:base + nxt] = r_start[:nxt], r_len[:nxt]
+        rel_score[base:base + nxt] = r_sum[:nxt] / np.maximum(r_len[:nxt], 1)
+        if stats is not None:
+            keep = np.nonzero(r_len[:nxt] >= MIN_MEMBERS)[0]
+            _gap_margin(stats, "score", rel_score[base + keep],
+                        lambda i, j: r_sum[keep[i]] == r_sum[keep[j]] and r_len[keep[i]] == r_len[keep[j]])
+    return rel_id, rel_start, rel_len, rel_score, n_rel
+
+
+def gather_relations(pk, rel_id, rel_start, rel_len, rel_score, n_rel, names=None):
+    """Per video: drop relations of fewer than 10 members, order the rest by score (descending, stable in creation order),
+    keep 200, and collect each one's trajectories and ``rel_idex`` from its members."""
+    out = {}
+    for v, vid in enumerate(pk.vids):
+        f0, f1 = int(pk.frame_off[v]), int(pk.frame_off[v + 1])
+        base, end = int(pk.pred_off[f0]), int(pk.pred_off[f1])
+        nr = int(n_rel[v])
+        keep = np.nonzero(rel_len[base:base + nr] >= MIN_MEMBERS)[0]
+        keep = keep[np.argsort(-rel_score[base + keep], kind="stable")][:MAX_PER_VIDEO]
+        ids = rel_id[base:end]
+        by_rel = np.argsort(ids, kind="stable")                  # members of a relation, in frame order
+        first = np.searchsorted(ids[by_rel], np.arange(nr + 1))
+        rels = []
+        for k in keep:
+            mem = base + by_rel[first[k]:first[k + 1]]
+            s, p, o = (int(x) for x in pk.triplet[mem[0]])
+            start = int(rel_start[base + k])
+            rels.append({
+                "triplet": [names[0][s], names[1][p], names[0][o]] if names is not None else [s, p, o],
+                "score": float(rel_score[base + k]),
+                "duration": [start, start + int(rel_len[base + k])],
+                "sub_traj": pk.boxes[mem, :4].tolist(),
+                "obj_traj": pk.boxes[mem, 4:].tolist(),
+                "rel_idex": list(pk.rel_idex[mem]),
+            })
+        out[vid] = rels
+    return out
+
+
+def associate(frame_relations, device=None, names=None, stats=None):
+    """``frame_relations``: {vid: [[fno, [[conf, [s, p, o], [sub_box, obj_box], rel_idex], ...]], ...]}.  Returns {vid:
+    [{triplet, score, duration, sub_traj, obj_traj, rel_idex}, ...]}, at most 200 per video in descending score; triplets
+    as ids, or as names with ``names=(objects, predicates)``.  ``device``: all videos in one kernel launch on that GPU;
+    None: the host implementation."""
+    pk = pack_frames(frame_relations)
+    if device is None:
+        res = associate_arrays_host(pk, stats)
+    else:
+        from . import ops
+        res = [t.cpu().numpy() for t in ops.video_associate(pk.frame_off, pk.frame_no, pk.pred_off, pk.score, pk.triplet,
+                                                            pk.boxes, device=device)]
+    return gather_relations(pk, *res, names=names)
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# evaluation
+# ------------------------------------------------------------------------------------------------------------------
+class PackedEval(object):
+    """Flat arrays of predictions and ground truths of the videos that have ground truth (``ops.video_viou_match``)."""
+
+    def __init__(self, vids, pred_off, pred_rel, pred_score, gt_off, gt_rel, boxes):
+        self.vids, self.pred_off, self.pred_rel, self.pred_score = vids, pred_off, pred_rel, pred_score
+        self.gt_off, self.gt_rel, self.boxes = gt_off, gt_rel, boxes
+
+
+def pack_eval(prediction, groundtruth):
+    vocab = {}
+    boxes, n_box = [], [0]
+
+    def rows(v, rels):
+        out = np.zeros((len(rels), REL_COLS), np.int32)
+        for k, r in enumerate(rels):
+            out[k, 0] = v
+            out[k, 1:4] = [vocab.setdefault(x, len(vocab)) for x in r["triplet"]]
+            out[k, 4:6] = r["duration"]
+            for c, key in ((6, "sub_traj"), (8, "obj_traj")):
+                out[k, c], out[k, c + 1] = n_box[0], len(r[key])
+                if len(r[key]):
+                    boxes.append(np.asarray(r[key], np.float64).reshape(-1, 4))
+                    n_box[0] += len(r[key])
+        return out
+
+    vids, pred_off, gt_off, pred_rel, gt_rel, score = [], [0], [0], [], [], []
+    for vid, gts in groundtruth.items():
+        if len(gts) == 0:                                # the reference skips a video without ground truth
+            continue
+        preds = prediction.get(vid, [])
+        v = len(vids)
+        vids.append(vid)
+        pred_rel.append(rows(v, preds))
+        gt_rel.append(rows(v, gts))
+        score.extend(float(r["score"]) for r in preds)
+        pred_off.append(pred_off[-1] + len(preds))
+        gt_off.append(gt_off[-1] + len(gts))
+    cat = lambda parts, shape: np.concatenate(parts) if parts else np.zeros(shape)
+    return PackedEval(vids, np.asarray(pred_off, np.int32), cat(pred_rel, (0, REL_COLS)).astype(np.int32),
+                      np.asarray(score, np.float64), np.asarray(gt_off, np.int32), cat(gt_rel, (0, REL_COLS)).astype(np.int32),
+                      cat(boxes, (0, 4)).astype(np.float64))
+
+
+def _viou(pr, gr, c, boxes, vol_p, vol_g):
+    """Voluminal IoU of one trajectory pair (+1 pixel convention): intersection over the common frames, volumes over the
+    whole trajectories."""
+    lo, hi = max(pr[4], gr[4]), min(pr[5], gr[5])
+    if hi <= lo:
+        return 0.0
+    n = max(0, min(hi - lo, pr[c + 1] - (lo - pr[4]), gr[c + 1] - (lo - gr[4])))     # never past the end of a trajectory
+    a = boxes[pr[c] + lo - pr[4]:pr[c] + lo - pr[4] + n]
+    b = boxes[gr[c] + lo - gr[4]:gr[c] + lo - gr[4] + n]
+    w = np.minimum(a[:, 2], b[:, 2]) - np.maximum(a[:, 0], b[:, 0]) + 1.0
+    h = np.minimum(a[:, 3], b[:, 3]) - np.maximum(a[:, 1], b[:, 1]) + 1.0
+    inter = float(np.sum(np.maximum(w, 0.0) * np.maximum(h, 0.0)))
+    return inter / (vol_p + vol_g - inter)
+
+
+def match_arrays_host(pe, viou_threshold=0.5, stats=None):
+    """The rules of ``ops.video_viou_match`` in numpy.  Returns (ov (n_pred, max_gt), hit (n_pred), hit_ov (n_pred)).
+    ``stats``: smallest relative margin of an ov against the threshold (``ov``) and between two unequal ov that one
+    prediction chooses from (``ov_gap``)."""
+    counts = np.diff(pe.gt_off)
+    max_gt = int(counts.max()) if len(counts) else 0
+    n_pred = len(pe.pred_rel)
+    ov = np.full((n_pred, max_gt), -1.0)
+    hit, hit_ov = np.full(n_pred, -1, np.int32), np.full(n_pred, -1.0)
+
+    def volumes(rel):
+        b = pe.boxes
+        area = (b[:, 2] - b[:, 0] + 1.0) * (b[:, 3] - b[:, 1] + 1.0)
+        return np.array([[area[r[c]:r[c] + r[c + 1]].sum() for c in (6, 8)] for r in rel]).reshape(-1, 2)
+
+    vp, vg = volumes(pe.pred_rel), volumes(pe.gt_rel)
+    for v in range(len(pe.vids)):
+        p0, p1, g0, g1 = int(pe.pred_off[v]), int(pe.pred_off[v + 1]), int(pe.gt_off[v]), int(pe.gt_off[v + 1])
+        for p in range(p0, p1):
+            pr = pe.pred_rel[p]
+            for g in np.nonzero((pe.gt_rel[g0:g1, 1:4] == pr[1:4]).all(1))[0]:
+                gr = pe.gt_rel[g0 + g]
+                s = _viou(pr, gr, 6, pe.boxes, vp[p, 0], vg[g0 + g, 0])
+                o = _viou(pr, gr, 8, pe.boxes, vp[p, 1], vg[g0 + g, 1])
+                ov[p, g] = min(s, o)
+        taken = np.zeros(g1 - g0, bool)
+        for p in p0 + np.argsort(-pe.pred_score[p0:p1], kind="stable"):
+            row = ov[p, :g1 - g0]
+            if stats is not None and (row >= 0).any():
+                x = row[row >= 0]
+                _note(stats, "ov", np.abs(x - viou_threshold).min() / max(viou_threshold, 1e-300))
+                u = np.unique(x[x >= viou_threshold])
+                if len(u) > 1:
+                    _note(stats, "ov_gap", (np.diff(u) / u[1:]).min())
+            cand = (row >= 0) & (row >= viou_threshold) & ~taken
+            if cand.any():
+                g = int(np.where(cand, row, -1.0).argmax())
+                taken[g] = True
+                hit[p], hit_ov[p] = g, row[g]
+    return ov, hit, hit_ov
+
+
+def match(prediction, groundtruth, viou_threshold=0.5, device=None, stats=None):
+    """Detection matching of every video that has ground truth: (PackedEval, ov, hit, hit_ov) with ``hit[p]`` the index of
+    the ground truth (within its video) that prediction p detects, or -1."""
+    pe = pack_eval(prediction, groundtruth)
+    if device is None:
+        return (pe,) + match_arrays_host(pe, viou_threshold, stats)
+    from . import ops
+    ov, hit, hit_ov = ops.video_viou_match(pe.pred_off, pe.pred_rel, pe.pred_score, pe.gt_off, pe.gt_rel, pe.boxes,
+                                           viou_threshold, device=device)
+    return pe, ov.cpu().numpy(), hit.cpu().numpy(), hit_ov.cpu().numpy()
+
+
+def voc_ap(rec, prec, use_07_metric=False):
+    """VOC average precision: the area under the precision envelope, or the 11-point mean of the 2007 devkit."""
+    rec, prec = np.asarray(rec), np.asarray(prec)
+    if use_07_metric:
+        ap = 0.
+        for t in np.arange(0., 1.1, 0.1):
+            above = rec >= t
+            ap = ap + (np.max(prec[above]) if above.any() else 0) / 11.
+        return ap
+    mrec = np.concatenate(([0.], rec, [1.]))
+    mpre = np.concatenate(([0.], prec, [0.]))
+    mpre = np.maximum.accumulate(mpre[::-1])[::-1]
+    i = np.nonzero(mrec[1:] != mrec[:-1])[0]
+    return np.sum((mrec[i + 1] - mrec[i]) * mpre[i + 1])
+
+
+def _prec_rec(tp, n_gt):
+    eps = np.finfo(np.float32).eps
+    cum_tp = np.cumsum(tp).astype(np.float32)
+    cum_fp = np.cumsum(~tp).astype(np.float32)
+    return cum_tp / np.maximum(cum_tp + cum_fp, eps), cum_tp / np.maximum(n_gt, eps)
+
+
+def _tagging_precision(gts, preds):
+    """Precision over the distinct predicted triplets in descending score; trajectories play no part."""
+    want = set(tuple(r["triplet"]) for r in gts)
+    seen, tp = set(), []
+    for r in sorted(preds, key=lambda r: r["score"], reverse=True):
+        t = tuple(r["triplet"])
+        if t not in seen:
+            seen.add(t)
+            tp.append(t in want)
+    return _prec_rec(np.asarray(tp, bool), len(want))[0]
+
+
+def evaluate(prediction, groundtruth, viou_threshold=0.5, det_nreturns=(50, 100), tag_nreturns=(1, 5, 10), device=None):
+    """(mean_ap, {n: detection recall@n}, {n: tagging precision@n}) over the videos of ``groundtruth`` that have relations."""
+    pe, _, hit, _ = match(prediction, groundtruth, viou_threshold, device)
+    video_ap, n_gt_total = [], 0
+    tp_at = dict((n, 0) for n in det_nreturns)
+    prec_at = dict((n, []) for n in tag_nreturns)
+    for v, vid in enumerate(pe.vids):
+        gts, preds = groundtruth[vid], prediction.get(vid, [])
+        p0, p1 = int(pe.pred_off[v]), int(pe.pred_off[v + 1])
+        n_gt_total += len(gts)
+        tp = (hit[p0:p1] >= 0)[np.argsort(-pe.pred_score[p0:p1], kind="stable")]
+        prec, rec = _prec_rec(tp, len(gts))
+        video_ap.append(voc_ap(rec, prec))
+        for n in det_nreturns:
+            tp_at[n] += int(tp[:n].sum())
+        tag = _tagging_precision(gts, preds)
+        for n in tag_nreturns:
+            cut = min(n, tag.size)
+            prec_at[n].append(tag[cut - 1] if cut > 0 else 0.)
+    mean_ap = np.mean(video_ap)
+    # recall@n is the last element of a cumulative sum over all videos' first n predictions: their order plays no part
+    rec_at_n = dict((n, np.float32(tp_at[n]) / np.maximum(n_gt_total, np.finfo(np.float32).eps)) for n in det_nreturns)
+    mprec_at_n = dict((n, np.mean(prec_at[n])) for n in tag_nreturns)
+    return mean_ap, rec_at_n, mprec_at_n

@@ -208,6 +208,42 @@ int32_t i2v_relation_topk(const float* rel_score, const float* conf, const int64
                           int32_t n_pairs, int32_t n_rel, int32_t k, int32_t* pair_out, int32_t* pred_out,
                           float* conf_out, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- video relations: association and the detection metric's matching (lib/utils.py) ----------------------------
+ * replaces greedy_relational_association (:134-182) for a packed batch of videos, one workgroup per video.
+ *   frame_off (n_videos+1): video v owns frames [frame_off[v], frame_off[v+1]), in ascending frame number;
+ *   frame_no (n_frames); pred_off (n_frames+1): frame f owns predictions [pred_off[f], pred_off[f+1]), at most
+ *   max_per_frame <= 100 of them (the caller cuts a longer list to its 100 best first); per prediction score (fp64),
+ *   triplet (3 x int32: s_cid, pid, o_cid) and boxes (8 x fp64: subject x1 y1 x2 y2, object x1 y1 x2 y2).
+ * A frame's predictions are taken in descending score, equal scores in the given order.  A prediction extends the open
+ * relation of largest current mean score (equal means: the one the previous frame touched first) that has its triplet,
+ * ended on the previous frame number and whose last subject AND object box have IoU >= 0.5 (no +1; fp64, the
+ * reference's operation order) with the prediction's; a relation serves one prediction per frame; otherwise the
+ * prediction opens a relation.  Outputs: rel_id (n_preds) = the relation of every prediction, numbered per video in
+ * creation order; relation k of video v is described at index pred_off[frame_off[v]] + k of rel_start (first frame
+ * number), rel_len (members) and rel_score (mean of the members' scores, summed in member order); n_rel (n_videos).
+ * Entries past a video's n_rel are not written.  The first int32 of the workspace is a status word: 0, or 1 + the index
+ * of a frame whose table entries were out of range (such a frame is skipped as if empty). */
+size_t  i2v_video_associate_workspace_bytes(int32_t n_videos, int32_t n_frames, int32_t n_preds);
+int32_t i2v_video_associate(const int32_t* frame_off, const int32_t* frame_no, const int32_t* pred_off,
+                            const double* score, const int32_t* triplet, const double* boxes,
+                            int32_t n_videos, int32_t n_frames, int32_t n_preds, int32_t max_per_frame,
+                            int32_t* rel_id, int32_t* rel_start, int32_t* rel_len, double* rel_score,
+                            int32_t* n_rel, void* workspace, size_t workspace_bytes, void* stream);
+/* replaces viou (:221-262) and the greedy loop of eval_detection_scores (:265-288).  A relation is a row of 10 int32:
+ * video, s_cid, pid, o_cid, fstart, fend, sub_off, sub_len, obj_off, obj_len; the trajectories are runs of `boxes`
+ * (n_boxes x 4 fp64).  Video v owns predictions [pred_off[v], pred_off[v+1]) (at most max_pred <= 200) and ground truths
+ * [gt_off[v], gt_off[v+1]) (at most max_gt <= 4096).  ov (n_pred x max_gt, fp64): min of the subject and object voluminal
+ * IoU (+1 pixel convention; volumes over whole trajectories, intersection over the common frames) where the triplets are
+ * equal, -1 elsewhere.  Predictions in descending score (equal scores in the given order) each take the not yet taken
+ * ground truth of largest ov >= viou_threshold (first index on equal ov): hit (n_pred) = its index within the video or
+ * -1, hit_ov (n_pred) = that ov or -1.  Status word as above (1 + the index of a video with out-of-range tables). */
+size_t  i2v_video_viou_match_workspace_bytes(int32_t n_pred, int32_t n_gt);
+int32_t i2v_video_viou_match(const int32_t* pred_off, const int32_t* pred_rel, const double* pred_score,
+                             const int32_t* gt_off, const int32_t* gt_rel, const double* boxes,
+                             int32_t n_videos, int32_t n_pred, int32_t n_gt, int64_t n_boxes, int32_t max_pred,
+                             int32_t max_gt, double viou_threshold, double* ov, int32_t* hit, double* hit_ov,
+                             void* workspace, size_t workspace_bytes, void* stream);
+
 /* IoU of boxes (B,N,4 | stride_box floats per row, first 4 used after `box_off`) against
  * gt (B,K,5): bbox_transform.py:168-257 (bbox_overlaps_batch) incl. the zero-area
  * masks; also emits per-row max/argmax (first max).  overlaps may be NULL. */

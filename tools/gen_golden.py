@@ -14,7 +14,8 @@ Two tiers, recorded per file in the ``tier`` field:
                  own text to gcc unmodified (no stand-in header, nothing of it written to disk but the .so)
                  lib/utils.py:584-628 ``detection_output``: the module cannot be imported (a module-level json.load of an
                  absolute path), so the function's own lines are compiled from the file and run unmodified, with the
-                 ``np.float`` alias numpy 1.24 removed restored for the call
+                 ``np.float`` alias numpy 1.24 removed restored for the call; the same for its video functions (_iou,
+                 VideoRelation, greedy_relational_association, association, viou, eval_*_scores, voc_ap, evaluate)
   "placeholders" the module imports after registering in-process placeholders for
                  three third-party packages absent from this image and for the
                  reference's un-buildable compiled extensions:
@@ -702,13 +703,180 @@ def gen_vrd(cfg):
         S.F.dropout = F_dropout
 
 
+# ----------------------------------------------------------------------------- video association / evaluation
+def _utils_functions(names):
+    """Functions (and the VideoRelation class) of lib/utils.py compiled from their own lines: the module cannot be imported
+    (a module-level json.load of an absolute path).  ``objects_list`` / ``predicates_list`` are plain id lists, so that
+    serialize() keeps ids; ``print`` is silenced."""
+    import ast
+    import collections
+    path = os.path.join(REF, "lib", "utils.py")
+    with open(path) as f:
+        tree = ast.parse(f.read(), path)
+    body = [n for n in tree.body if isinstance(n, (ast.FunctionDef, ast.ClassDef)) and n.name in names]
+    assert len(body) == len(names)
+    ns = {"np": np, "json": __import__("json"), "defaultdict": collections.defaultdict, "print": lambda *a, **k: None,
+          "objects_list": list(range(64)), "predicates_list": list(range(200))}
+    exec(compile(ast.Module(body=body, type_ignores=[]), path, "exec"), ns)
+    return ns
+
+
+def gen_video():
+    """tests/golden/video_association.npz and video_eval.npz: the reference's association() and evaluate() on the videos of
+    i2vsgg_amd.synthetic.video_fixture_cases().  The inputs are regenerated from seeds; the files hold the reference's
+    results (relations as triplet, score, duration and, per member, which input prediction its boxes are), the frames
+    after its fill of empty ones, and the smallest margin of the decisions that rest on computed doubles."""
+    import copy
+    import json
+    import tempfile
+    import time
+    from i2vsgg_amd import video
+    MARGIN = 1e-9
+    ns = _utils_functions(["_iou", "VideoRelation", "greedy_relational_association", "voc_ap", "viou", "eval_detection_scores",
+                           "eval_tagging_scores", "evaluate", "association"])
+    cases = syn.video_fixture_cases()
+    iou_margin = [np.inf]
+    ref_iou = ns["_iou"]
+
+    def iou_logged(a, b):                                # every IoU the reference computes, against its threshold
+        v = ref_iou(a, b)
+        iou_margin[0] = min(iou_margin[0], abs(v - 0.5) / 0.5)
+        return v
+    ns["_iou"] = iou_logged
+    out = {"vids": np.array(list(cases))}
+    frame_off, filled_src, rel_off, trip, score, dur, mem_off, mem_frame, mem_pred = [0], [], [0], [], [], [], [0], [], []
+    margins = {"iou": np.inf, "mean": np.inf, "score": np.inf}
+    facts = {"kept_max": 0, "len9": 0, "len10": 0, "contested": 0, "multi_candidate": 0, "ties_mean": 0, "score_ties_in_frame": 0,
+             "over_100": 0, "stays_empty": 0, "filled": 0, "gap": 0}
+    predictions = {}
+    for vid, frames in cases.items():
+        # the package's host form on the same input: the margins of the mean / score comparisons (its sums run in member
+        # order, the reference's np.mean pairwise: decisions closer than MARGIN could differ and may not enter the file)
+        st = {"exact_sums": all(p[0] * 64 == int(p[0] * 64) for f in frames for p in f[1])}
+        pk = video.pack_frames(copy.deepcopy({vid: frames}))
+        res = video.associate_arrays_host(pk, st)
+        for k in margins:
+            margins[k] = min(margins[k], st.get(k, np.inf))
+        lens = res[2][:int(res[4][0])]
+        facts["kept_max"] = max(facts["kept_max"], int((lens >= 10).sum()))
+        facts["len9"] += int((lens == 9).sum())
+        facts["len10"] += int((lens == 10).sum())
+        for k in ("contested", "multi_candidate", "ties_mean"):
+            facts[k] += st.get(k, 0)
+        facts["over_100"] += sum(len(f[1]) > 100 for f in frames)
+        facts["score_ties_in_frame"] += sum(len(set(p[0] for p in f[1])) < len(f[1]) for f in frames)
+        nos = sorted(int(f[0]) for f in frames)
+        facts["gap"] += sum(b - a > 1 for a, b in zip(nos, nos[1:]))
+        # the reference, on lists of its own
+        mine = copy.deepcopy(frames)
+        mine.sort(key=lambda x: int(x[0]))
+        where, lists = {}, {}
+        for i, f in enumerate(mine):
+            lists[id(f[1])] = i
+            for j, p in enumerate(f[1]):
+                where[id(p[2][0])] = (i, j, 0)
+                where[id(p[2][1])] = (i, j, 1)
+        was_empty = [len(f[1]) == 0 for f in mine]
+        t0 = time.time()
+        rels = ns["association"]({vid: mine})[vid]
+        print("    association %-6s %3d frames -> %3d relations (%.1f s)" % (vid, len(mine), len(rels), time.time() - t0))
+        for i, f in enumerate(mine):                     # association() fills its argument in place
+            src = lists[id(f[1])]
+            filled_src.append(src if len(f[1]) else -1)
+            facts["stays_empty"] += len(f[1]) == 0
+            facts["filled"] += was_empty[i] and len(f[1]) > 0
+        frame_off.append(len(filled_src))
+        for r in rels:
+            trip.append(r["triplet"])
+            score.append(r["score"])
+            dur.append(r["duration"])
+            for s, o in zip(r["sub_traj"], r["obj_traj"]):
+                ws, wo = where[id(s)], where[id(o)]
+                assert ws[:2] == wo[:2] and ws[2] == 0 and wo[2] == 1
+                mem_frame.append(ws[0])
+                mem_pred.append(ws[1])
+            mem_off.append(len(mem_frame))
+        rel_off.append(len(trip))
+        predictions[vid] = rels
+    margins["iou"] = min(margins["iou"], iou_margin[0])
+    print("    margins", margins, "facts", facts)
+    assert min(margins.values()) >= MARGIN, "a decision within %g of its threshold: choose another seed" % MARGIN
+    assert facts["kept_max"] > 200 and facts["len9"] and facts["len10"] and facts["contested"] and facts["multi_candidate"]
+    assert facts["ties_mean"] and facts["score_ties_in_frame"] and facts["over_100"] and facts["stays_empty"] and facts["filled"]
+    assert facts["gap"]
+    moved = [r for r in predictions["moved"] if r["triplet"] == [3, 60, 4]]
+    assert sorted(r["duration"] for r in moved) == [[0, 25], [25, 60]]       # the object moved away, the subject stayed
+    save("video_association", "extracted", frame_off=np.asarray(frame_off, np.int32), filled_src=np.asarray(filled_src, np.int32),
+         rel_off=np.asarray(rel_off, np.int32), triplet=np.asarray(trip, np.int32), score=np.asarray(score, np.float64),
+         duration=np.asarray(dur, np.int32), mem_off=np.asarray(mem_off, np.int32), mem_frame=np.asarray(mem_frame, np.int16),
+         mem_pred=np.asarray(mem_pred, np.int16), margin_iou=np.float64(margins["iou"]), margin_mean=np.float64(margins["mean"]),
+         margin_score=np.float64(margins["score"]), **out)
+
+    # ---- evaluation: the reference's predictions against ground truth made from them; one video has none
+    gts = dict((vid, syn.video_groundtruth(predictions[vid], 300 + k)) for k, vid in enumerate(predictions))
+    gts["v07"] = []
+    thr = 0.5
+    st = {}
+    pe, ov_h, hit_h, _ = video.match(predictions, gts, thr, stats=st)
+    assert min(st.get("ov", 1), st.get("ov_gap", 1)) >= MARGIN, st
+    ov_ref = np.full(ov_h.shape, np.nan)
+    tp_ref = np.zeros(len(hit_h), bool)
+    ref_viou = ns["viou"]
+    calls = []
+    ns["viou"] = lambda t1, d1, t2, d2: calls.append((id(t1), id(t2), ref_viou(t1, d1, t2, d2))) or calls[-1][2]
+    lens = []
+    for v, vid in enumerate(pe.vids):
+        preds, g = predictions[vid], gts[vid]
+        pid = dict((id(r[key]), (k, c)) for k, r in enumerate(preds) for c, key in enumerate(("sub_traj", "obj_traj")))
+        gid = dict((id(r[key]), (k, c)) for k, r in enumerate(g) for c, key in enumerate(("sub_traj", "obj_traj")))
+        del calls[:]
+        _, _, hit_scores = ns["eval_detection_scores"](g, preds, thr)
+        order = np.argsort(-np.array([r["score"] for r in preds]), kind="stable")
+        p0 = int(pe.pred_off[v])
+        tp_ref[p0 + order] = np.isfinite(hit_scores)
+        for (a, b, val), (a2, b2, val2) in zip(calls[0::2], calls[1::2]):
+            assert pid[a][0] == pid[a2][0] and gid[b][0] == gid[b2][0] and pid[a][1] == 0 and pid[a2][1] == 1
+            ov_ref[p0 + pid[a][0], gid[b][0]] = min(val, val2)
+        lens += [len(r["sub_traj"]) for r in preds]
+    # the reference computes an overlap exactly for the ground truths of equal triplet that are not yet detected; with the
+    # package's hit list the same cells must be the computed ones, and the same predictions the true positives
+    assert ((hit_h >= 0) == tp_ref).all()
+    seen = ~np.isnan(ov_ref)
+    assert np.allclose(ov_ref[seen], ov_h[seen], rtol=1e-12, atol=0)
+    for v in range(len(pe.vids)):
+        p0, p1 = int(pe.pred_off[v]), int(pe.pred_off[v + 1])
+        taken = set()
+        for p in p0 + np.argsort(-pe.pred_score[p0:p1], kind="stable"):
+            want = set(g for g in np.nonzero(ov_h[p] >= 0)[0] if g not in taken)
+            assert want == set(np.nonzero(seen[p])[0]), (v, p)
+            if hit_h[p] >= 0:
+                taken.add(int(hit_h[p]))
+    n_over = np.array([(ov_h[:, g] >= thr).sum() for g in range(ov_h.shape[1])])
+    assert (hit_h < 0).any() and (ov_h.max(1) < 0).any() and min(lens) == 10 and max(lens) >= 500
+    both = [(ov_h[int(pe.pred_off[v]):int(pe.pred_off[v + 1])] >= thr).sum(0).max() for v in range(len(pe.vids))]
+    assert max(both) >= 2                                # two predictions over one ground truth
+    assert ((ov_h > 0) & (ov_h < thr)).any()             # a partial overlap
+    with tempfile.NamedTemporaryFile("w", suffix=".json", delete=False) as f:
+        json.dump(gts, f)
+    try:
+        mean_ap, rec, mprec = ns["evaluate"](predictions, f.name, thr)
+    finally:
+        os.unlink(f.name)
+    print("    evaluate: mAP %.6f  R@50 %.6f  R@100 %.6f  P@1 %.6f  P@5 %.6f  P@10 %.6f" % (
+        mean_ap, rec[50], rec[100], mprec[1], mprec[5], mprec[10]))
+    save("video_eval", "extracted", vids=np.array(pe.vids), pred_off=pe.pred_off, hit=hit_h.astype(np.int32), ov=ov_ref,
+         metrics=np.array([mean_ap, rec[50], rec[100], mprec[1], mprec[5], mprec[10]], np.float64), viou_threshold=np.float64(thr),
+         gt_seed_base=np.int32(300), no_gt=np.array(["v07"]), margin_ov=np.float64(st.get("ov", np.inf)),
+         margin_ov_gap=np.float64(st.get("ov_gap", np.inf)))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--only", default="")
     a = ap.parse_args()
     os.makedirs(GOLD, exist_ok=True)
     todo = a.only.split(",") if a.only else ["direct", "roialign", "roialign_fresh", "tails", "rpn", "nets", "full", "ctx", "step",
-                                             "vrd"]
+                                             "vrd", "video"]
     if "direct" in todo:
         print("[direct imports]")
         gen_direct()
@@ -721,6 +889,9 @@ def main():
     if "tails" in todo:
         print("[eval tails: direct imports + detection_output compiled from its own lines]")
         gen_eval_tails()
+    if "video" in todo:
+        print("[video association / evaluation: lib/utils.py functions compiled from their own lines]")
+        gen_video()
     if any(t in todo for t in ("rpn", "nets", "full", "vrd", "ctx", "step")):
         print("[imports with placeholders]")
         cfg = install_placeholders()
