@@ -6,7 +6,7 @@ legacy default stream that path loses the order between a graph's nodes and the 
 stream is busy (DESIGN.md section 5 has the bisect and the A/B runs; measured cost of the generic path on the 330-node
 step graph: none).  A value the user has set is left alone, and so is a process whose HIP runtime is already up.
 Whether the runtime READ the value cannot be known from here (``torch.cuda.is_available()`` initialises it without torch
-saying so), so ``train.replay_graph`` does not rely on it: a replay asked for on the default stream always runs on a private
+saying so), so ``graphs.replay_graph`` does not rely on it: a replay asked for on the default stream always runs on a private
 stream between two event edges."""
 import os
 import sys

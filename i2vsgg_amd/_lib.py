@@ -146,7 +146,7 @@ TUNE = {"I2V_CONV_SPEC": 0, "I2V_SPLIT_TARGET": 1, "I2V_SPLIT_TARGET_SKINNY": 2,
 # experiment kernels that left the library in round 6 (the library refuses any value but "off").
 ENV_TUNE = ("I2V_SPLIT_ATOMICS", "I2V_SPLIT_TARGET", "I2V_SPLIT_TARGET_SKINNY", "I2V_SPLIT_BELOW", "I2V_BIG_FC_TILE",
             "I2V_WGRAD_FUSED_TILE", "I2V_WGRAD_PER_CU", "I2V_KGROUPS", "I2V_WGRAD_ORDERED_GFLOP", "I2V_WINO_ROWS", "I2V_GEMM_DMA", "I2V_WGRAD_DMA", "I2V_ROIALIGN_BWD", "I2V_NMS_SCAN")
-# Settled A/B switches of rounds 1-5 that no longer read the environment (their comments in ops.py / train.py name the module
+# Settled A/B switches of rounds 1-5 that no longer read the environment (their comments in ops.py / train.py / optim.py name the module
 # attribute that replaced them).  A run that still sets one would measure the default without knowing (round-5 advice): say so.
 RETIRED_ENV = ("I2V_WINOGRAD_TRAIN", "I2V_BLOCK_FUSED", "I2V_WINOGRAD_WGRAD", "I2V_KEEP_V", "I2V_WGRAD_BRANCH", "I2V_ISD_BATCHED",
                "I2V_DEFER_FC", "I2V_EXPERIMENTS")

@@ -14,6 +14,7 @@ import numpy as np
 import torch
 
 from . import ops
+from .graphs import GraphRecorder, replay_graph
 from .model.utils.config import cfg
 
 
@@ -29,7 +30,7 @@ class _FrameShape:
         self.tick = 0
 
 
-class _FrameGraphStep:
+class _FrameGraphStep(GraphRecorder):
     """Shared machinery of ``DetectStep`` / ``RelationStep``: ``frames`` independent per-frame bodies (``_frame(fs, f)``, written by
     the subclass against static device buffers) as one HIP graph per frame size with a branch per frame; at most ``max_graphs``
     sizes are kept (least recently used goes first), their graphs share one memory pool (no two ever run at once)."""
@@ -74,7 +75,7 @@ class _FrameGraphStep:
         """The device front-end of ``roibatchLoader(training=False, device_prep=True)`` items: uint8 frames as decoded cross PCIe,
         BGR swap / mean subtraction / resize run in ``i2v_image_prep``.  ``meta`` rows: [flipped, canvas_h, canvas_w, scale,
         target]; the frames of a call share their canvas.  -> (frame set, the (n,3) im_info rows)."""
-        from .train import _Uploader, _place_u8
+        from .staging import _Uploader, _place_u8
         meta = np.asarray(meta.cpu() if torch.is_tensor(meta) else meta, np.float64).reshape(-1, 5)
         n = len(frames_u8)
         if n > self.frames or len(meta) != n:
@@ -109,17 +110,7 @@ class _FrameGraphStep:
         if not self.use_graph:
             fs.graph = False
             return
-        try:
-            g = torch.cuda.CUDAGraph()
-            if self._pool is None:
-                self._pool = torch.cuda.graph_pool_handle()
-            with torch.cuda.graph(g, pool=self._pool):
-                self._body(fs)
-            fs.graph = g
-        except Exception as e:                     # report, keep the eager form for this size
-            fs.graph, self.graph_error = False, repr(e)
-            ops.reset_branches()
-            torch.cuda.synchronize(self.dev)
+        fs.graph = self._record_graph(lambda: self._body(fs))      # False (``graph_error``): the eager form for this size
 
     def _run_staged(self):
         fs = self.shapes[self._staged]
@@ -128,7 +119,6 @@ class _FrameGraphStep:
         self._tick += 1
         fs.tick = self._tick
         if fs.graph:
-            from .train import replay_graph
             replay_graph(fs.graph, self.dev)
         else:
             self._body(fs)
@@ -251,7 +241,7 @@ class RelationStep(_FrameGraphStep):
         self._alloc(int(cap_boxes))
 
     def _alloc(self, cap_boxes):
-        from .train import _Slot
+        from .staging import _Slot
         F_, cb = self.frames, max(int(cap_boxes), 3)
         cp = (cb - 1) * (cb - 2)
         self.cap_boxes, self.cap_pairs = cb, cp

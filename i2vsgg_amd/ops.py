@@ -394,7 +394,7 @@ class ZeroArena:
         return t
 
 
-# Bumped whenever trained parameters change behind autograd's back (train.FusedSGD writes through raw device pointers and
+# Bumped whenever trained parameters change behind autograd's back (optim.FusedSGD writes through raw device pointers and
 # never touches ``Tensor._version``): part of the key of every cache derived from a trained parameter.
 PARAM_EPOCH = 0
 
@@ -726,7 +726,7 @@ def _conv_wgrad_raw(x, g, w_shape, stride, pad, tag="wgrad", row_scale=None, win
 
 
 # parameter storage pointer -> (momentum buffer, lr, momentum, weight_decay): filters whose SGD update is
-# fused into their wgrad epilogue (train.FusedSGD.fuse_wgrad); their .grad is then never materialised
+# fused into their wgrad epilogue (optim.FusedSGD.fuse_wgrad); their .grad is then never materialised
 FUSED_SGD = {}
 
 

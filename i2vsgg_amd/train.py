@@ -7,438 +7,18 @@
 
 Both keep their inputs resident on the device, can be captured into a HIP graph (the step is launch
 bound otherwise: ~300 small kernels), and all-reduce gradients over RCCL when world_size > 1.
+The capture machinery they share is ``graphs.CapturedStep``; the optimizers (optim.py), the staging helpers (staging.py)
+and ``replay_graph`` are imported here under the names callers have always used (``train.FusedSGD``, ...).
 """
 import numpy as np
 import torch
 
 from . import _lib, ops, parallel
 from . import synthetic as syn
+from .graphs import CapturedStep, replay_graph, _REPLAY_STREAMS                                   # noqa: F401
 from .model.utils.config import cfg
-
-
-
-class FusedSGD:
-    """SGD(momentum) with the reference's param groups (bias: lr x2 and no weight decay when
-    cfg.TRAIN.DOUBLE_BIAS / not BIAS_DECAY) on the fused HIP kernel; one launch per tensor."""
-
-    def __init__(self, named_params, lr, momentum=None, weight_decay=None):
-        T = cfg.TRAIN
-        self.momentum = T.MOMENTUM if momentum is None else momentum
-        wd = T.WEIGHT_DECAY if weight_decay is None else weight_decay
-        self.items = []
-        self._fused_keys = []
-        for name, p in named_params:
-            if not p.requires_grad:
-                continue
-            is_bias = "bias" in name
-            p._i2v_trained = True        # updated through raw device pointers: caches keyed on p._version also key on ops.PARAM_EPOCH
-            self.items.append(dict(
-                name=name, p=p, m=torch.zeros_like(p),
-                lr=lr * ((T.DOUBLE_BIAS + 1) if is_bias else 1),
-                wd=(wd if T.BIAS_DECAY else 0.0) if is_bias else wd))
-
-    def fuse_wgrad(self, min_numel=1 << 24):
-        """Fuse the update of large filters into their wgrad epilogue (single-GPU only: with data
-        parallelism the gradient must be all-reduced before the update).  Returns the fused names.
-        (Rounds 3-5 carried a second form, ``defer``: the update applied by the NEXT forward on its pass over the filter --
-        parity-tested, 1.41 ms against 0.43 + 0.79 as two kernels, never used; it left the tree in round 6, DESIGN_HISTORY.md 5.6.)"""
-        names = []
-        for it in self.items:
-            p = it["p"]
-            if parallel.exchange_enabled() and not parallel.is_local(p):
-                continue              # its gradient has to cross the ranks first
-            if p.dim() >= 2 and p.numel() >= min_numel:
-                # keyed by storage pointer (what the autograd node sees); ``owner`` says whose entry it is -- a pointer is
-                # reused by the allocator, and an optimizer that is collected late must not remove (or act on) the entry a
-                # newer optimizer made for a new filter at the same address
-                ops.FUSED_SGD[p.data_ptr()] = ops.FusedEntry(it["m"], it["lr"], self.momentum, it["wd"], self)
-                self._fused_keys.append(p.data_ptr())
-                names.append(it["name"])
-        return names
-
-    def _mine(self, table, k):
-        ent = table.get(k)
-        return ent if ent is not None and getattr(ent, "owner", None) is self else None
-
-    def flush_pending(self):
-        """Nothing is pending: every update is applied inside the step (rounds 3-5 had a deferred form for fc6 / fc7; callers that
-        read filters outside the step keep calling this)."""
-
-    def pending_state(self):
-        return [], []
-
-    def restore_pending(self, host):
-        pass
-
-    def unfuse(self):
-        for k in self._fused_keys:
-            if self._mine(ops.FUSED_SGD, k) is not None:      # not an entry a newer optimizer made at a reused address
-                del ops.FUSED_SGD[k]
-        self._fused_keys = []
-
-    def __del__(self):
-        try:
-            self.unfuse()
-        except Exception:
-            pass
-
-    def params(self):
-        return [it["p"] for it in self.items]
-
-    def state_tensors(self):
-        """Every tensor of the optimizer's own state (a step object snapshots / restores them around warm-up steps)."""
-        return [it["m"] for it in self.items]
-
-    @staticmethod
-    def bump():
-        """The parameters changed (an eager ``step()``, a fused wgrad+SGD epilogue or a graph replay that contains
-        them): whatever is derived from trained parameters and cached (Winograd-domain filters) is stale."""
-        ops.PARAM_EPOCH += 1
-
-    def state_dict(self):
-        """torch.optim.SGD's layout (param_groups + state[i]['momentum_buffer']) in named_parameters order, so that a
-        checkpoint written here resumes under torch.optim.SGD and vice versa."""
-        self.flush_pending()
-        return {"state": {i: {"momentum_buffer": it["m"].detach().clone()} for i, it in enumerate(self.items)},
-                "param_groups": [{"lr": it["lr"], "momentum": self.momentum, "weight_decay": it["wd"], "params": [i],
-                                  "name": it["name"]} for i, it in enumerate(self.items)]}
-
-    def load_state_dict(self, sd):
-        self.flush_pending()
-        groups = sd["param_groups"]
-        flat = [pi for g in groups for pi in g["params"]]
-        if len(flat) != len(self.items):
-            raise ValueError("optimizer state holds %d parameters, this optimizer %d" % (len(flat), len(self.items)))
-        by_param = {pi: g for g in groups for pi in g["params"]}
-        for i, it in enumerate(self.items):
-            g = by_param[flat[i]]
-            it["lr"], it["wd"] = float(g["lr"]), float(g.get("weight_decay", it["wd"]))
-            self.momentum = float(g.get("momentum", self.momentum))
-            st = sd["state"].get(flat[i], sd["state"].get(str(flat[i])))
-            if st is not None and st.get("momentum_buffer") is not None:
-                it["m"].copy_(st["momentum_buffer"].reshape(it["m"].shape))
-            else:
-                it["m"].zero_()
-        for k in list(self._fused_keys):       # fused entries hold (momentum, lr, ...) by value
-            for it in self.items:
-                if it["p"].data_ptr() == k and self._mine(ops.FUSED_SGD, k) is not None:
-                    ops.FUSED_SGD[k] = ops.FusedEntry(it["m"], it["lr"], self.momentum, it["wd"], self)
-
-    def zero_grad(self):
-        for it in self.items:
-            it["p"].grad = None
-
-    def lr_of(self, name):
-        """The learning rate the optimizer holds for parameter ``name`` (what a resumed run shows and decays from)."""
-        for it in self.items:
-            if it["name"] == name:
-                return it["lr"]
-        return self.items[0]["lr"]
-
-    def scale_lr(self, k):
-        self.flush_pending()            # a pending update belongs to the step that computed it: applied at that step's rate
-        for it in self.items:
-            it["lr"] *= k
-            ent = self._mine(ops.FUSED_SGD, it["p"].data_ptr())
-            if ent is not None:                 # fused entries hold the rate by value (a captured graph holds it too:
-                ops.FUSED_SGD[it["p"].data_ptr()] = ops.FusedEntry(ent[0], it["lr"], ent[2], ent[3], self)   # re-capture after a decay)
-
-    MULTI_BELOW = 1 << 20       # tensors under 1 Mi elements share one launch
-
-    @torch.no_grad()
-    def step(self):
-        small = []
-        for it in self.items:
-            p, g = it["p"], it["p"].grad
-            if g is None:
-                continue
-            if g.stride() != p.stride() and not _same_memory_order(p, g):
-                g = torch.empty_like(p).copy_(g)
-            if p.numel() < self.MULTI_BELOW:
-                small.append((p, g, it))
-            else:
-                ops.sgd_momentum_(p, g, it["m"], it["lr"], self.momentum, it["wd"])
-        if small:
-            ops.sgd_momentum_multi_([p for p, _, _ in small], [g for _, g, _ in small], [it["m"] for _, _, it in small],
-                                    [it["lr"] for _, _, it in small], [it["wd"] for _, _, it in small], self.momentum)
-        self.bump()
-
-
-class FusedAdam(FusedSGD):
-    """torch.optim.Adam with the reference's param groups (``--o adam``: trainval_net_instance_styleD_bilinear.py:143-145,
-    trainval_net_SGG_emb.py:146-147) on ``i2v_adam_multi``: same interface as ``FusedSGD`` towards the step objects, no fusion
-    into the filter-gradient kernels (the second-moment update needs the finished gradient).  The step count sits in device
-    memory, so a captured step replays with the right bias corrections; ``state_dict`` is torch.optim.Adam's layout."""
-
-    def __init__(self, named_params, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=None):
-        super().__init__(named_params, lr, momentum=0.0, weight_decay=weight_decay)
-        self.betas, self.eps = (float(betas[0]), float(betas[1])), float(eps)
-        for it in self.items:
-            it["v"] = torch.zeros_like(it["p"])
-        dev = self.items[0]["p"].device if self.items else "cpu"
-        self.t = torch.zeros(1, dtype=torch.int32, device=dev)
-
-    def fuse_wgrad(self, min_numel=1 << 24, defer=None):
-        return []
-
-    def state_tensors(self):
-        return [it["m"] for it in self.items] + [it["v"] for it in self.items] + [self.t]
-
-    def state_dict(self):
-        # torch.optim.Adam holds state only for parameters that have received a gradient (round-3 advice); its per-parameter
-        # ``step`` is one shared device counter here -- every trained parameter of the two reference models gets a gradient
-        # every step, so the two agree
-        step = float(self.t.item())
-        return {"state": {i: {"step": torch.tensor(step), "exp_avg": it["m"].detach().clone(), "exp_avg_sq": it["v"].detach().clone()}
-                          for i, it in enumerate(self.items) if it.get("seen")},
-                "param_groups": [{"lr": it["lr"], "betas": self.betas, "eps": self.eps, "weight_decay": it["wd"], "amsgrad": False,
-                                  "maximize": False, "foreach": None, "capturable": False, "differentiable": False, "fused": None,
-                                  "params": [i], "name": it["name"]} for i, it in enumerate(self.items)]}
-
-    def load_state_dict(self, sd):
-        groups = sd["param_groups"]
-        flat = [pi for g in groups for pi in g["params"]]
-        if len(flat) != len(self.items):
-            raise ValueError("optimizer state holds %d parameters, this optimizer %d" % (len(flat), len(self.items)))
-        by_param = {pi: g for g in groups for pi in g["params"]}
-        step = 0.0
-        for i, it in enumerate(self.items):
-            g = by_param[flat[i]]
-            it["lr"], it["wd"] = float(g["lr"]), float(g.get("weight_decay", it["wd"]))
-            self.betas, self.eps = tuple(float(b) for b in g.get("betas", self.betas)), float(g.get("eps", self.eps))
-            st = sd["state"].get(flat[i], sd["state"].get(str(flat[i])))
-            if st is not None and st.get("exp_avg") is not None:
-                it["m"].copy_(st["exp_avg"].reshape(it["m"].shape))
-                it["v"].copy_(st["exp_avg_sq"].reshape(it["v"].shape))
-                step = max(step, float(st.get("step", 0.0)))
-                it["seen"] = True
-            else:
-                it["m"].zero_()
-                it["v"].zero_()
-                it["seen"] = False
-        self.t.fill_(int(step))
-
-    def scale_lr(self, k):
-        for it in self.items:
-            it["lr"] *= k
-
-    @torch.no_grad()
-    def step(self):
-        live = []
-        for it in self.items:
-            p, g = it["p"], it["p"].grad
-            if g is None:                        # torch.optim.Adam skips parameters without a gradient
-                continue
-            if g.stride() != p.stride() and not _same_memory_order(p, g):
-                g = torch.empty_like(p).copy_(g)
-            it["seen"] = True
-            live.append((p, g, it))
-        if not live:
-            return
-        ops.adam_step_(self.t)
-        ops.adam_multi_([p for p, _, _ in live], [g for _, g, _ in live], [it["m"] for _, _, it in live],
-                        [it["v"] for _, _, it in live], [it["lr"] for _, _, it in live], [it["wd"] for _, _, it in live],
-                        self.betas, self.eps, self.t)
-        self.bump()
-
-
-def make_optimizer(kind, named_params, lr):
-    """``--o sgd | adam`` of the reference loops."""
-    if kind == "sgd":
-        return FusedSGD(named_params, lr)
-    if kind == "adam":
-        return FusedAdam(named_params, lr)
-    raise ValueError("optimizer %r: the reference loops know 'sgd' and 'adam'" % (kind,))
-
-
-def _same_memory_order(p, g):
-    """Two dense tensors of one shape whose strides agree on every axis longer than 1 hold their elements in the same order
-    in memory (a (Cout,Cin,1,1) filter gradient in channels_last strides against the parameter's plain strides): the flat
-    update kernels may read both as they are.  Without this every 1x1 filter gradient of the trunk was copied once per step
-    (45 launches, 0.2 ms of the instance_styleD step: tools/glue_trace.py)."""
-    if p.shape != g.shape or p.numel() != g.numel():
-        return False
-    for n, sp, sg in zip(p.shape, p.stride(), g.stride()):
-        if n > 1 and sp != sg:
-            return False
-    dense = lambda t: t.is_contiguous() or (t.dim() == 4 and t.is_contiguous(memory_format=torch.channels_last))
-    return dense(p) and dense(g)
-
-
-def synthetic_sgg_batch(seed, n_frames, n_boxes=32, n_pairs=32, n_rel=62, n_cls=16, h=600, w=1000):
-    """frames + per-frame annotation dicts (keys ``f0..``) + im_info."""
-    im, info = syn.frames(seed, n_frames, h, w)
-    annos = {"f%d" % i: syn.relation_annotation(seed * 1000 + i, n_boxes, n_pairs, n_rel, n_cls, h, w)
-             for i in range(n_frames)}
-    return im, info, annos
-
-
-def sgg_head_inputs(annos, info, n_rel):
-    """Head inputs of one minibatch on the host, exact sizes (faster_rcnn_SGG_emb.py:170-245 for every frame of the batch;
-    frames without an annotated relation contribute nothing, :177-183): ``annos`` one annotation dict per frame (unscaled
-    pixel boxes, as in the ``source_gt_rels`` pickle), ``info`` (n_frames,3) im_info rows [h, w, scale].
-    -> dict of numpy arrays: boxes (nb,5), relb (np,5) [frame index in column 0], labels (np,n_rel), ixs / ixo (np,) rows of
-    ``boxes``, bounds (np,2,4) integer bounds of the 32x32 dual masks, wrow (np,) = 1 / (pairs of the frame * frames with
-    pairs): sum_r wrow[r] * mean_c BCE is the mean over frames of the per-frame BCE mean."""
-    from .model.faster_rcnn.faster_rcnn_SGG_emb import build_pair_tables
-    boxes, relb, bounds, labels, ixs, ixo, counts, off = [], [], [], [], [], [], [], 0
-    for f, anno in enumerate(annos):
-        if anno is None or len(anno["rels"]) < 1:
-            continue
-        gt, union, bnd, lab, s, o = build_pair_tables(anno, float(info[f][2]), float(info[f][0]), float(info[f][1]), n_rel)
-        b5 = np.zeros((gt.shape[0], 5), np.float32); b5[:, 0] = f; b5[:, 1:] = gt
-        r5 = np.zeros((union.shape[0], 5), np.float32); r5[:, 0] = f; r5[:, 1:] = union
-        boxes.append(b5); relb.append(r5); bounds.append(bnd); labels.append(lab)
-        ixs.append(s + off); ixo.append(o + off); counts.append(lab.shape[0]); off += gt.shape[0]
-    if not counts:
-        return None
-    cat = np.concatenate
-    return dict(boxes=cat(boxes), relb=cat(relb), labels=cat(labels).astype(np.float32), ixs=cat(ixs).astype(np.int64),
-                ixo=cat(ixo).astype(np.int64), bounds=cat(bounds).astype(np.int32),
-                wrow=cat([np.full((c,), 1.0 / (c * len(counts)), np.float32) for c in counts]))
-
-
-def _rasterize_host(bounds, channels=4):
-    """(n,2,4) integer [x1,y1,x2,y2) -> (n,channels,32,32) float32 dual masks (resnet_SGG_emb.py:246-256); channels 2.. are
-    the zero pad that keeps conv_lo.0's gathers 16-byte wide."""
-    n = bounds.shape[0]
-    m = np.zeros((n, channels, 32, 32), np.float32)
-    ar = np.arange(32)
-    b = bounds.reshape(n, 2, 4, 1)
-    xs = (ar[None, None, :] >= b[:, :, 0]) & (ar[None, None, :] < b[:, :, 2])          # (n,2,32)
-    ys = (ar[None, None, :] >= b[:, :, 1]) & (ar[None, None, :] < b[:, :, 3])
-    m[:, :2] = (ys[:, :, :, None] & xs[:, :, None, :]).astype(np.float32)
-    return m
-
-
-class _Slot:
-    """One minibatch worth of head inputs packed into ONE device buffer (256-B aligned fields), so that moving a
-    batch between pipeline stages is a single copy whatever the number of fields.  ``layout``: name -> (shape, dtype).
-    ``host=True`` adds two pinned host mirrors of the same layout: a batch is assembled in one of them and crosses PCIe as
-    ONE asynchronous copy."""
-
-    def __init__(self, layout, device, host=False):
-        self.layout = {k: (tuple(sh), dt) for k, (sh, dt) in layout.items()}
-        self.spec, off = [], 0
-        for name, (shape, dt) in self.layout.items():
-            nbytes = int(np.prod(shape)) * torch.empty((), dtype=dt).element_size()
-            self.spec.append((name, off, nbytes, dt, shape))
-            off += (nbytes + 255) // 256 * 256
-        self.nbytes = max(off, 256)
-        self.buf = torch.zeros(self.nbytes, dtype=torch.uint8, device=device)
-        self.views = {name: self.buf[o:o + n].view(dt).view(shape) for name, o, n, dt, shape in self.spec}
-        self._host, self._turn = [], 0
-        if host:
-            for _ in range(2):
-                hb = torch.zeros(self.nbytes, dtype=torch.uint8).pin_memory()
-                hv = {name: hb[o:o + n].view(dt).view(shape).numpy() for name, o, n, dt, shape in self.spec}
-                self._host.append((hb, hv, torch.cuda.Event()))
-
-    def same_layout(self, layout):
-        return self.layout == {k: (tuple(sh), dt) for k, (sh, dt) in layout.items()}
-
-    def write(self, fields):
-        """Device tensors of exactly the slot's shapes (one small copy per field)."""
-        for name, t in fields.items():
-            self.views[name].copy_(t)
-
-    def write_host(self, fields):
-        """numpy arrays, each at most as large as its field along axis 0: zero-padded to the slot's capacity in a pinned
-        mirror, then ONE asynchronous H2D copy on the current stream."""
-        hb, hv, ev = self._host[self._turn]
-        self._turn ^= 1
-        ev.synchronize()                         # the copy that last read this mirror has finished (two calls ago)
-        for name, a in fields.items():
-            dst = hv[name]
-            n = a.shape[0] if a.ndim else 0
-            if a.ndim and n > dst.shape[0]:
-                raise ValueError("field %s: %d rows exceed the slot's capacity %d" % (name, n, dst.shape[0]))
-            if a.ndim:
-                dst[:n] = a
-                dst[n:] = 0
-            else:
-                dst[...] = a
-        self.buf.copy_(hb, non_blocking=True)
-        ev.record()
-
-
-class _Uploader:
-    """Host frames -> device on the process's COPY stream (ops.role_stream), two staging buffers and event edges both ways: the
-    transfer of minibatch k+1 runs beside the step that is still computing (a 2 x 3 x 600 x 1000 fp32 minibatch is 14.4 MB;
-    bench.py --data loader over four alternating frame sizes: 5.00 -> 4.82 ms per step, uint8 frames 4.83 -> 4.77).
-    ``I2V_UPLOAD_STREAM=0``: the transfer on the caller's stream, in front of the step (the default of round 3, which had met
-    a host segfault in hipGraphLaunch with the copy stream and blamed stream aliasing).  The same file order with pooled
-    streams and every alias logged -- the copy stream WAS a captured branch, the side stream WAS torch's capture stream --
-    neither crashes (profiles/r04_alias_repro.txt; that record stopped on a bookkeeping KeyError of the test before the numeric
-    comparison) nor changes a loss or a weight (profiles/r05_alias_repro.txt: run to the end, 18 passed) once no graph is
-    dropped while a replay of it may be in flight (``invalidate_graphs`` synchronises first; stage() grew the head capacity
-    and dropped every graph right behind an asynchronous replay).  The aliases cost the overlap, not correctness; they are gone too (ops.role_stream),
-    and tests/test_gpu_data_layer.py runs the loader loop both ways, in the order that crashed.
-    ``upload`` returns a device tensor that is valid on the caller's CURRENT stream, ``consumed`` marks the point after which
-    its buffer may be overwritten."""
-
-    def __init__(self, device):
-        self.dev = torch.device(device)
-        # Normal priority.  Measured (tools/loader_probe.py, relation step, 14.4 MB of frames per step): the transfer costs the
-        # step 0.35-0.4 ms although it is queued a step ahead on its own stream -- it runs as a blit kernel and only gets its
-        # turn when the step's branches drain.  A HIGH-priority copy stream (I2V_UPLOAD_PRIORITY=-1) hides it when every
-        # minibatch has one size (4.74 -> 4.86 ms instead of 5.15) but doubles the step (8.7-9.5 ms) as soon as the loop
-        # alternates between the graphs of two sizes -- so it is not the default.
-        import os
-        self.enabled = os.environ.get("I2V_UPLOAD_STREAM", "1") == "1"
-        # the copy stream exists only when asked for, and is the process's ONE copy stream (ops.role_stream): a handle of the
-        # library's own, never an alias of a branch / capture / communicator stream out of torch's pool
-        self.stream = ops.role_stream(self.dev, "copy", 0) if self.enabled else None      # normal priority: a high one doubles the step when the loop alternates between the graphs of two sizes (DESIGN.md 5.5)
-        self.rings = {}
-
-    def upload(self, frames):
-        if not self.enabled:                 # the transfer on the caller's stream, in front of the step (the round-2 form)
-            return frames.to(self.dev, non_blocking=True), None
-        return self._upload(frames)
-
-    def _upload(self, frames):
-        # ONE ring of two byte buffers for every shape: upload k+2 waits for the consumer of upload k whatever their shapes, so
-        # at most two transfers are ever queued ahead of the step
-        nbytes = frames.numel() * frames.element_size()
-        ring = self.rings.setdefault("ring", {"i": 0, "buf": [None, None], "free": [None, None]})
-        i = ring["i"]
-        ring["i"] ^= 1
-        cur = torch.cuda.current_stream(self.dev)
-        if ring["free"][i] is not None:
-            self.stream.wait_event(ring["free"][i])          # the copy that last READ this buffer (two uploads ago) is done
-        with torch.cuda.stream(self.stream):
-            if ring["buf"][i] is None or ring["buf"][i].numel() < nbytes:
-                # allocated ON the copy stream (the caching allocator hands a block only to work ordered behind its previous
-                # use on the stream it was allocated for) and known to the consumer's stream, so that a release -- growth
-                # here, or the end of the step object -- waits for both
-                ring["buf"][i] = torch.empty(max(nbytes, 1 << 20), dtype=torch.uint8, device=self.dev)
-            ring["buf"][i].record_stream(cur)
-            dst = ring["buf"][i][:nbytes].view(frames.dtype).view(frames.shape)
-            dst.copy_(frames, non_blocking=True)
-            done = torch.cuda.Event()
-            done.record(self.stream)
-        cur.wait_event(done)
-        return dst, (ring, i)
-
-    def consumed(self, token):
-        if token is None:
-            return
-        ring, i = token
-        ev = torch.cuda.Event()
-        ev.record(torch.cuda.current_stream(self.dev))
-        ring["free"][i] = ev
-
-
-def _place_u8(uploader, frames_u8, meta, dst):
-    """The device front-end of a ``roibatchLoader(device_prep=True)`` minibatch: every decoded uint8 frame crosses PCIe as it
-    is (copy stream) and ``i2v_image_prep`` writes the mean-subtracted, resized BGR image into its slot of ``dst`` (n,4,H,W)
-    channels_last, which is cleared first (the canvas around an image is zero padding, roibatchLoader.py:162-181)."""
-    dst.zero_()
-    for f, u8 in enumerate(frames_u8):
-        flipped, target = bool(meta[f][0]), int(meta[f][4])
-        src, token = uploader.upload(u8)
-        ops.image_prep(src, cfg.PIXEL_MEANS, target, flipped=flipped, rgb=True, blob=dst[f:f + 1])
-        uploader.consumed(token)
+from .optim import FusedSGD, FusedAdam, make_optimizer, _same_memory_order                       # noqa: F401
+from .staging import _Slot, _Uploader, _place_u8, synthetic_sgg_batch, sgg_head_inputs, _rasterize_host    # noqa: F401
 
 
 class _FrameSet:
@@ -461,6 +41,10 @@ class _FrameSet:
         self.ctx_back = ops.LaunchContext(device, arena=arena)
         self.fitted_front = self.fitted_back = False
         self.graphs = {}              # back size key -> graph (or False)
+
+    def drop_graphs(self):
+        self.graph = None
+        self.graphs.clear()
 
 
 class _StagePipeline:
@@ -495,7 +79,7 @@ class _StagePipeline:
         return head
 
 
-class SGGEmbStep:
+class SGGEmbStep(CapturedStep):
     """One step of trainval_net_SGG_emb.py:189-255 (pre_det) as a replayable object.
 
     A step = one backbone pass (no grad: the reference detaches the feature map, faster_rcnn_SGG_emb.py:148), one
@@ -1024,20 +608,8 @@ class SGGEmbStep:
         self._fmap_key, self._mid_key = fb.key, fs.key
 
     # ------------------------------------------------------------------ capture
-    def invalidate_graphs(self):
-        """Drop every captured graph (a learning-rate change -- rates live in the captured kernel arguments --, a capacity
-        change, new feature-map buffers).  They are captured again on first use."""
-        dropped = any(fs.graph for fs in self.shapes.values())
-        if dropped:
-            torch.cuda.synchronize(self.dev)      # a replay may still be running: its executable graph goes only after it
-        for fs in self.shapes.values():
-            fs.graph = None
-            fs.graphs.clear()
-        if dropped:
-            import gc
-            gc.collect()
-            torch.cuda.synchronize(self.dev)
-        self._pool = None             # the allocator releases a pool with its last graph: the next capture opens a new one
+    def _graph_holders(self):
+        return self.shapes.values()
 
     def capture(self, warmup=2, restore=False):
         """Warm up eagerly (sizes the arenas, fills the allocator), then capture the step for the staged frame size into ONE
@@ -1046,28 +618,12 @@ class SGGEmbStep:
         steps on the staged batch; put parameters, momentum and the RNG state back afterwards (a training loop that must
         not see them).  ``warmup=0`` re-captures (after a learning-rate change: rates live in the captured kernel
         arguments)."""
-        saved = None
-        if restore and warmup:
-            saved = self._snapshot()
+        saved = self._snapshot() if (restore and warmup) else None
         try:
             return self._capture(warmup)
         finally:
             if saved is not None:
-                self._restore(saved)
-
-    def _snapshot(self):
-        pend, host = self.opt.pending_state()
-        state = [it["p"].data for it in self.opt.items] + self.opt.state_tensors() + pend
-        return (state, [t.clone() for t in state], torch.cuda.get_rng_state(self.dev), host)
-
-    def _restore(self, saved):
-        torch.cuda.synchronize(self.dev)
-        with torch.no_grad():
-            for t, sv in zip(saved[0], saved[1]):
-                t.copy_(sv)
-        torch.cuda.set_rng_state(saved[2], self.dev)
-        self.opt.restore_pending(saved[3])
-        self.opt.bump()
+                self._restore(saved)      # AFTER the recording: it changes no training state here (_capture_frames)
 
     def _capture(self, warmup):
         if self.tp:
@@ -1077,16 +633,7 @@ class SGGEmbStep:
         fs = self.shapes[self._staged]
         self._measure(fs)
         pipelined, self._pipelined = self._pipelined, False     # the warm-up steps are sequential eager steps
-        s = ops.role_stream(self.dev, "warmup")
-        s.wait_stream(torch.cuda.current_stream(self.dev))
-        with torch.cuda.stream(s):
-            for i in range(warmup):
-                self._body()
-                if i == 0:
-                    self.ctx_bb.fit()
-                    self.ctx_head.fit()
-        torch.cuda.current_stream(self.dev).wait_stream(s)
-        torch.cuda.synchronize(self.dev)
+        self._warm_up(warmup, self._body, lambda: (self.ctx_bb.fit(), self.ctx_head.fit()))
         self._pipelined = pipelined
         if not self.use_graph:
             return False
@@ -1134,94 +681,60 @@ class SGGEmbStep:
             fs.fitted_front = fb.fitted_back = True
             torch.cuda.synchronize(self.dev)
         fs.fitted = True
-        if staged:
-            live = [(f, k) for f in self.shapes.values() for k, g in f.graphs.items() if g]
-            if len(live) >= self.max_graphs:                      # least recently used pair goes
-                torch.cuda.synchronize(self.dev)
-                f, k = min(live, key=lambda fk: fk[0].tick)
-                f.graphs[k] = None
-                if f.graph is not None and not any(f.graphs.values()):
-                    f.graph = None
+        if staged:                    # a graph per (front size, back size) pair
+            old = self._evict_lru([(f, k) for f in self.shapes.values() for k, g in f.graphs.items() if g])
+            if old is not None and old.graph is not None and not any(old.graphs.values()):
+                old.graph = None      # its last pair graph went
         else:
-            live = [f for f in self.shapes.values() if f.graph]
-            if len(live) >= self.max_graphs:                          # least recently used goes (after whatever is still running)
-                torch.cuda.synchronize(self.dev)
-                min(live, key=lambda f: f.tick).graph = None
+            self._evict_lru([(f, None) for f in self.shapes.values() if f.graph])
+        if self._pipelined and self._side is None:
+            self._side = ops.role_stream(self.dev, "side")
         fmap_key = self._fmap_key
-        try:
-            g = torch.cuda.CUDAGraph()
-            if self._pool is None:
-                self._pool = torch.cuda.graph_pool_handle()
-            torch.cuda.synchronize(self.dev)
-            parallel.wait_for_collectives(self.dev)
-            if self._pipelined:
-                if self._side is None:
-                    self._side = ops.role_stream(self.dev, "side")
-                with torch.cuda.graph(g, pool=self._pool, **parallel.capture_kwargs()):
-                    self._body_overlapped(fs)
-            else:
-                with torch.cuda.graph(g, pool=self._pool, **parallel.capture_kwargs()):
-                    self._rotate()
-                    self._backbone(fs)
-                    self._head()
-            fs.graph = g
-            if staged:
-                fs.graphs[fb.key] = g
-            return True
-        except Exception as e:      # report, fall back to eager launches for this size
-            fs.graph = False
-            if staged:
-                fs.graphs[fb.key] = False
-            self.graph_error = repr(e)
-            ops.reset_branches()
-            torch.cuda.synchronize(self.dev)
-            return False
+        try:                          # (the recording starts with a device synchronisation: the fitting passes above are finished)
+            g = self._record_graph((lambda: self._body_overlapped(fs)) if self._pipelined else self._body)      # fs is the staged set
         finally:
             self._fmap_key = fmap_key        # recording is not running: the buffer still holds what it held
+        fs.graph = g                  # False: eager launches for this size
+        if staged:
+            fs.graphs[fb.key] = g
+        return bool(g)
 
-    def __call__(self):
-        """One step on the caller's current stream (any stream, the legacy default stream included: see
-        ``replay_graph``).  Returns the device scalar holding the loss of the batch the head just processed.
+    def _step(self):
+        """A call of the step.  Returns the device scalar holding the loss of the batch the head just processed.
         Before a successful ``capture()`` a call is the sequential eager step."""
         fs = self.shapes[self._staged]
-        try:
-            if self._graphs_on and self._pipelined and self.stage_split:
-                self._measure(fs)
-                if self._pipe.call() is None:
-                    self._fill_call(fs)              # the pipeline fills: both backbone halves, no head
-                    self.n_bubbles += 1
-                else:
-                    fb_key = self._mid_key
-                    if fs.graphs.get(fb_key) is None:
-                        self._capture_frames(fs)     # first sight of this (front size, back size) pair
-                    g = fs.graphs.get(fb_key)
-                    self._tick += 1
-                    fs.tick = self._tick
-                    fs.graph = g if g else fs.graph
-                    if g:
-                        replay_graph(g, self.dev)
-                    else:
-                        self._body_overlapped(fs)    # this pair could not be captured: the same schedule on eager launches
-                    self._fmap_key, self._mid_key = fb_key, fs.key
-            elif self._graphs_on:
-                if fs.graph is None:
-                    self._capture_frames(fs)         # first sight of this frame size (or the graphs were invalidated)
+        if self._graphs_on and self._pipelined and self.stage_split:
+            self._measure(fs)
+            if self._pipe.call() is None:
+                self._fill_call(fs)              # the pipeline fills: both backbone halves, no head
+                self.n_bubbles += 1
+            else:
+                fb_key = self._mid_key
+                if fs.graphs.get(fb_key) is None:
+                    self._capture_frames(fs)     # first sight of this (front size, back size) pair
+                g = fs.graphs.get(fb_key)
                 self._tick += 1
                 fs.tick = self._tick
-                if fs.graph:
-                    replay_graph(fs.graph, self.dev)
-                    self._fmap_key = fs.key
-                elif self._pipelined:
-                    self._body_overlapped(fs)        # this size could not be captured: the same schedule on eager launches
+                fs.graph = g if g else fs.graph
+                if g:
+                    replay_graph(g, self.dev)
                 else:
-                    self._body()
+                    self._body_overlapped(fs)    # this pair could not be captured: the same schedule on eager launches
+                self._fmap_key, self._mid_key = fb_key, fs.key
+        elif self._graphs_on:
+            if fs.graph is None:
+                self._capture_frames(fs)         # first sight of this frame size (or the graphs were invalidated)
+            self._tick += 1
+            fs.tick = self._tick
+            if fs.graph:
+                replay_graph(fs.graph, self.dev)
+                self._fmap_key = fs.key
+            elif self._pipelined:
+                self._body_overlapped(fs)        # this size could not be captured: the same schedule on eager launches
             else:
                 self._body()
-        except BaseException:
-            # an eager body that raised between a branch and its join leaves process-wide role streams marked open
-            # (ops._FORKED): every later step object on this device would be refused its branches
-            ops.reset_branches()
-            raise
+        else:
+            self._body()
         self.opt.bump()
         return self.loss
 
@@ -1247,34 +760,6 @@ def run_staged(step, stagers, keep):
             keep[trained].copy_(loss)
             trained += 1
     return keep
-
-
-_REPLAY_STREAMS = {}
-REDIRECT_DEFAULT_STREAM = True      # tools/graph_order_probe.py studies the runtime's default path and switches this off
-
-
-def replay_graph(graph, device=None):
-    """``graph.replay()`` on the caller's current stream -- except on the LEGACY DEFAULT stream, where the replay runs on a
-    private stream between two event edges (the caller's stream order is kept).  ROCm 7.2's HIP runtime replays a graph through
-    pre-built AQL packet batches (``DEBUG_CLR_GRAPH_PACKET_CAPTURE``, on by default); on the legacy default stream that path loses
-    the order between a graph's nodes and the stream's other work while a second stream is busy (losses
-    off by 2e-2 from the second step on, NaN weights; the same graphs are correct on any created stream).
-    i2vsgg_amd/__init__.py switches the path off before the runtime initialises WHEN IT CAN -- but what the runtime actually
-    read cannot be told from os.environ (``torch.cuda.is_available()`` / ``device_count()`` bring the runtime up without setting
-    ``torch.cuda.is_initialized()``; a script may set the variable after its first HIP call), so the variable is not trusted
-    as proof (round-3 advice): every replay asked for on the default stream is redirected.  Cost: two event edges per step."""
-    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-    cur = torch.cuda.current_stream(dev)
-    if not REDIRECT_DEFAULT_STREAM or cur.cuda_stream != torch.cuda.default_stream(dev).cuda_stream:
-        graph.replay()
-        return
-    s = _REPLAY_STREAMS.get(dev.index)
-    if s is None:
-        s = _REPLAY_STREAMS[dev.index] = ops.role_stream(dev, "replay")
-    s.wait_stream(cur)
-    with torch.cuda.stream(s):
-        graph.replay()
-    cur.wait_stream(s)
 
 
 class _SplitBatch(torch.autograd.Function):
@@ -1321,8 +806,11 @@ class _DomainSet:
         self.fitted = False
         self.tick = 0
 
+    def drop_graphs(self):
+        self.graph = None
 
-class InstanceStyleDStep:
+
+class InstanceStyleDStep(CapturedStep):
     """One D+G adversarial step (trainval_net_instance_styleD_bilinear.py:262-341): source forward with
     detection + RPN losses and 0.5*mean(d^2) for both discriminators, target forward with
     0.5*mean((1-d)^2), style terms weighted by style_lambda, ONE backward through the gradient-reversal
@@ -1614,33 +1102,8 @@ class InstanceStyleDStep:
         atl.image_size = self.info0 if on else None
         self.net.RCNN_proposal_target.device_sampling = on
 
-    def _snapshot(self):
-        pend, host = self.opt.pending_state()
-        state = [it["p"].data for it in self.opt.items] + self.opt.state_tensors() + pend
-        return (state, [t.clone() for t in state], torch.cuda.get_rng_state(self.dev), host)
-
-    def _restore(self, saved):
-        torch.cuda.synchronize(self.dev)
-        with torch.no_grad():
-            for t, sv in zip(saved[0], saved[1]):
-                t.copy_(sv)
-        torch.cuda.set_rng_state(saved[2], self.dev)
-        self.opt.restore_pending(saved[3])
-        self.opt.bump()
-
-    def invalidate_graphs(self):
-        """Drop every captured graph (a learning-rate change: the rates live in the captured kernel arguments); they are
-        captured again on first use, into the same memory pool."""
-        dropped = any(ds.graph for ds in self.sets.values())
-        if dropped:
-            torch.cuda.synchronize(self.dev)      # a replay may still be running: its executable graph goes only after it
-        for ds in self.sets.values():
-            ds.graph = None
-        if dropped:
-            import gc
-            gc.collect()
-            torch.cuda.synchronize(self.dev)
-        self._pool = None             # the allocator releases a pool with its last graph: the next capture opens a new one
+    def _graph_holders(self):
+        return self.sets.values()
 
     def capture(self, warmup=2, restore=False):
         """Device-side target sampling, eager warm-up, then the whole step for the staged sizes as ONE HIP graph (other
@@ -1659,66 +1122,42 @@ class InstanceStyleDStep:
 
     def _capture_set(self, ds, warmup, restore):
         saved = self._snapshot() if (restore and warmup) else None
+        body = self._body_branches if self.branches else self._body
+
+        def fit():
+            if not ds.fitted:
+                for ctx in (ds.ctx, ds.ctx_src, ds.ctx_tgt):
+                    if ctx is not None:
+                        ctx.fit()
+                ds.fitted = True
         try:
             self._device_sampling(True)
-            body = self._body_branches if self.branches else self._body
-            s = ops.role_stream(self.dev, "warmup")
-            s.wait_stream(torch.cuda.current_stream(self.dev))
-            with torch.cuda.stream(s):
-                for i in range(warmup):
-                    body()
-                    if i == 0 and not ds.fitted:
-                        for ctx in (ds.ctx, ds.ctx_src, ds.ctx_tgt):
-                            if ctx is not None:
-                                ctx.fit()
-                        ds.fitted = True
-            torch.cuda.current_stream(self.dev).wait_stream(s)
-            torch.cuda.synchronize(self.dev)
+            self._warm_up(warmup, body, fit)
         finally:
             if saved is not None:
-                self._restore(saved)
-        live = [d for d in self.sets.values() if d.graph]
-        if len(live) >= self.max_graphs:                          # least recently used goes (after whatever is still running)
-            torch.cuda.synchronize(self.dev)
-            min(live, key=lambda d: d.tick).graph = None
-        try:
-            g = torch.cuda.CUDAGraph()
-            if self._pool is None:
-                self._pool = torch.cuda.graph_pool_handle()
-            parallel.wait_for_collectives(self.dev)
-            with torch.cuda.graph(g, pool=self._pool, **parallel.capture_kwargs()):
-                body()
-            ds.graph = g
-            return True
-        except Exception as e:
-            ds.graph = False
-            self.graph_error = repr(e)
-            ops.reset_branches()
-            torch.cuda.synchronize(self.dev)
-            return False
+                self._restore(saved)      # BEFORE the recording: it registers torch's generator (device-side sampling), so the RNG state in force may matter
+        self._evict_lru([(d, None) for d in self.sets.values() if d.graph])
+        ds.graph = self._record_graph(body)      # (synchronises the device first, on the warmup=0 path too); False: eager launches for this key
+        return bool(ds.graph)
 
-    def __call__(self):
+    def _step(self):
         ds = self._cur
-        try:
-            if self._graphs_on:
-                if ds.graph is None:
-                    # first sight of this pair of sizes (or the graphs were invalidated): one eager step sizes its arenas and
-                    # fills the host-built caches, its effect on the training state is undone, then the step is recorded
-                    self._capture_set(ds, 0 if ds.fitted else 1, True)
-                if ds.graph:
-                    replay_graph(ds.graph, self.dev)
-                else:
-                    self._device_sampling(True)
-                    (self._body_branches if self.branches else self._body)()
-                self.opt.bump()
+        if self._graphs_on:
+            if ds.graph is None:
+                # first sight of this pair of sizes (or the graphs were invalidated): one eager step sizes its arenas and
+                # fills the host-built caches, its effect on the training state is undone, then the step is recorded
+                self._capture_set(ds, 0 if ds.fitted else 1, True)
+            if ds.graph:
+                replay_graph(ds.graph, self.dev)
             else:
-                self._body()
-                if not ds.fitted:           # eager use: size the arena of atomically accumulated outputs after the first step
-                    ds.ctx.fit()
-                    ds.fitted = True
-        except BaseException:
-            ops.reset_branches()            # a body that raised between a branch and its join: see SGGEmbStep.__call__
-            raise
+                self._device_sampling(True)
+                (self._body_branches if self.branches else self._body)()
+            self.opt.bump()
+        else:
+            self._body()
+            if not ds.fitted:           # eager use: size the arena of atomically accumulated outputs after the first step
+                ds.ctx.fit()
+                ds.fitted = True
         return self.losses["total"]
 
 
