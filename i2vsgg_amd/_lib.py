@@ -90,6 +90,10 @@ SIGNATURES = {
     "i2v_video_associate": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _z, _p]),
     "i2v_video_viou_match_workspace_bytes": (_z, [_i, _i]),
     "i2v_video_viou_match": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _l, _i, _i, C.c_double, _p, _p, _p, _p, _z, _p]),
+    "i2v_det_eval_match_workspace_bytes": (_z, [_i]),
+    "i2v_det_eval_match": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, C.c_double, _p, _p, _p, _p, _z, _p]),
+    "i2v_det_eval_curve_workspace_bytes": (_z, [_i]),
+    "i2v_det_eval_curve": (_i, [_p, _p, _p, _p, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _z, _p]),
     "i2v_image_prep_size": (_i, [_i, _i, _i, _p, _p, _p]),
     "i2v_image_prep": (_i, [_p, _i, _i, _i, _i, _p, _i, _p, _i, _i, _p]),
     "i2v_det_postprocess_workspace_bytes": (_z, [_i, _i]),

@@ -1348,10 +1348,10 @@ def _to_dev(x, dtype, device):
     return torch.as_tensor(x).to(device=device, dtype=dtype).contiguous()
 
 
-def _video_status(ws, what):
+def _video_status(ws, what, entry="entry"):
     bad = int(ws[:4].view(torch.int32).item())              # the caller reads the results next anyway
     if bad:
-        raise _lib.I2VError("%s: the offset tables are out of range at entry %d" % (what, bad - 1))
+        raise _lib.I2VError("%s: the offset tables are out of range at %s %d" % (what, entry, bad - 1))
 
 
 def video_associate(frame_off, frame_no, pred_off, score, triplet, boxes, device=None):
@@ -1408,6 +1408,63 @@ def video_viou_match(pred_off, pred_rel, pred_score, gt_off, gt_rel, boxes, viou
         if V > 0 and NP > 0:
             _video_status(ws, "video_viou_match")
     return ov, hit, hit_ov
+
+
+def _det_eval_device(device, what):
+    dev = torch.device(device if device is not None else "cuda")
+    if dev.type != "cuda":
+        raise _lib.I2VError("i2vsgg_amd ops run on the GPU only (got device %s); detection_eval.%s is the host form" % (dev, what))
+    return dev
+
+
+def det_eval_match(seg_det_off, seg_gt, gt_off, det_key, det_box, gt_box, gt_hard, ovthresh=0.5, device=None):
+    """The VOC match of every detection against the ground truths of its class and image, one wave per (class, image)
+    segment (include/i2vsgg_hip.h, i2v_det_eval_match; ``detection_eval.pack`` builds the arrays).  Arrays or tensors:
+    seg_det_off (S+1), seg_gt (S), gt_off (slots+1), det_key (D), gt_hard (G) int32; det_box (D,4), gt_box (G,4) fp64.
+    Returns device tensors at the detections' own positions: (flag (D) int32: 1 tp, 2 fp, 0 neither; ovmax (D) fp64;
+    jmax (D) int32)."""
+    dev = _det_eval_device(device, "match_arrays_host")
+    gc = np.diff(np.asarray(torch.as_tensor(gt_off).cpu()))
+    max_gt = int(gc.max()) if len(gc) else 0
+    seg_det_off, seg_gt, gt_off = (_to_dev(x, torch.int32, dev) for x in (seg_det_off, seg_gt, gt_off))
+    det_key, gt_hard = _to_dev(det_key, torch.int32, dev), _to_dev(gt_hard, torch.int32, dev)
+    det_box, gt_box = _to_dev(det_box, torch.float64, dev), _to_dev(gt_box, torch.float64, dev)
+    S, D, NS, G = seg_gt.numel(), det_key.numel(), gt_off.numel() - 1, gt_hard.numel()
+    if seg_det_off.numel() != S + 1 or NS < 0 or det_box.numel() != 4 * D or gt_box.numel() != 4 * G:
+        raise ValueError("det_eval_match: array sizes do not agree")
+    flag = torch.full((D,), 2, device=dev, dtype=torch.int32)
+    ovmax = torch.full((D,), float("-inf"), device=dev, dtype=torch.float64)
+    jmax = torch.full((D,), -1, device=dev, dtype=torch.int32)
+    with torch.cuda.device(dev):
+        ws = workspace(lib.i2v_det_eval_match_workspace_bytes(D), dev, "det_eval")
+        check(lib.i2v_det_eval_match(ptr(seg_det_off), ptr(seg_gt), ptr(gt_off), ptr(det_key), ptr(det_box), ptr(gt_box),
+                                     ptr(gt_hard), S, D, NS, G, max_gt, float(ovthresh), ptr(flag), ptr(ovmax), ptr(jmax),
+                                     ptr(ws), ws.numel(), stream()), "det_eval_match")
+        if S > 0 and D > 0:
+            _video_status(ws, "det_eval_match", "segment")
+    return flag, ovmax, jmax
+
+
+def det_eval_curve(det_key, cls_off, flag, npos, device=None):
+    """Per class: the stable score order, cumulative tp / fp, recall, precision and both VOC AP forms
+    (include/i2vsgg_hip.h, i2v_det_eval_curve).  det_key (D), cls_off (C+1), flag (D), npos (C) int32.  Returns device
+    tensors (perm, cum_tp, cum_fp (D) int32, rec, prec (D) fp64, ap_area, ap_11pt (C) fp64)."""
+    dev = _det_eval_device(device, "curve_arrays_host")
+    det_key, cls_off, flag, npos = (_to_dev(x, torch.int32, dev) for x in (det_key, cls_off, flag, npos))
+    D, C = det_key.numel(), cls_off.numel() - 1
+    if C < 0 or flag.numel() != D or npos.numel() != C:
+        raise ValueError("det_eval_curve: array sizes do not agree")
+    perm, cum_tp, cum_fp = (torch.zeros((D,), device=dev, dtype=torch.int32) for _ in range(3))
+    rec, prec = (torch.zeros((D,), device=dev, dtype=torch.float64) for _ in range(2))
+    ap_area, ap_11pt = (torch.zeros((C,), device=dev, dtype=torch.float64) for _ in range(2))
+    with torch.cuda.device(dev):
+        ws = workspace(lib.i2v_det_eval_curve_workspace_bytes(D), dev, "det_eval")
+        check(lib.i2v_det_eval_curve(ptr(det_key), ptr(cls_off), ptr(flag), ptr(npos), C, D, ptr(perm), ptr(cum_tp), ptr(cum_fp),
+                                     ptr(rec), ptr(prec), ptr(ap_area), ptr(ap_11pt), ptr(ws), ws.numel(), stream()),
+              "det_eval_curve")
+        if C > 0:
+            _video_status(ws, "det_eval_curve", "class")
+    return perm, cum_tp, cum_fp, rec, prec, ap_area, ap_11pt
 
 
 class _L2NormRowsFn(torch.autograd.Function):

@@ -86,6 +86,23 @@ class SyntheticImdb:
     def set_proposal_method(self, method):
         assert method == "gt"
 
+    def evaluate_detections(self, all_boxes, output_dir, ovthresh=0.5, use_07_metric=False, device="auto"):
+        """What ends the detector test loop (the reference's imdb.evaluate_detections): VOC AP per class and the mean, from
+        ``all_boxes[class][image]`` and this imdb's own roidb.  Prints the reference's lines, writes ``<cls>_pr.pkl`` and
+        ``detection_eval.json`` into ``output_dir`` and returns the result of ``detection_eval.evaluate``.  Runs on
+        ``cuda:0`` when there is one, else on the host."""
+        import os
+        import torch
+        from .. import detection_eval
+        if device == "auto":
+            device = "cuda:0" if torch.cuda.is_available() else None
+        n = len(all_boxes[0]) if len(all_boxes) else 0
+        res = detection_eval.evaluate(all_boxes, self.roidb[:n], self.classes, ovthresh, use_07_metric, device)
+        os.makedirs(output_dir, exist_ok=True)
+        print("VOC07 metric? " + ("Yes" if use_07_metric else "No"))
+        detection_eval.report(res, self.classes, output_dir)
+        return res
+
     def append_flipped_images(self):
         n = self.num_images
         for i in range(n):

@@ -244,6 +244,37 @@ int32_t i2v_video_viou_match(const int32_t* pred_off, const int32_t* pred_rel, c
                              int32_t max_gt, double viou_threshold, double* ov, int32_t* hit, double* hit_ov,
                              void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- VOC detection evaluation that ends the detector test loop (lib/datasets/voc_eval.py:132-212) ----------------
+ * Detections lie in results-file order (class, then image, then row; i2vsgg_amd/detection_eval.py pack()): det_key
+ * (n_det int32) is the score as the results file would hold it ('%.3f'), in thousandths; det_box (n_det x 4 fp64) the
+ * box as the file would hold it ('%.1f' of coordinate + 1).  Segment s, one (class, image) pair with detections, owns
+ * detections [seg_det_off[s], seg_det_off[s+1]) and the ground truths [gt_off[k], gt_off[k+1]) of slot k = seg_gt[s]
+ * (n_slots slots, at most max_gt <= 4096 ground truths in one); gt_box (n_gt x 4 fp64, annotation + 1), gt_hard (n_gt int32).
+ * One wave per segment walks its detections in descending key (equal keys: results-file order) and writes, at each
+ * detection's own position, ovmax (the largest +1-convention IoU, fp64 in the reference's operation order; -inf without
+ * ground truth), jmax (the first ground truth that has it, within the slot; -1 without) and flag: 1 a true positive
+ * (ovmax > ovthresh, that ground truth not hard and not yet claimed), 2 a false positive, 0 neither (it is hard).
+ * Sized for the test loop's segments (at most max_per_image = 100 detections): a segment of n detections is ranked by one
+ * wave with n * n / 64 key comparisons, so any n is correct but a segment of tens of thousands would run for seconds.
+ * The first int32 of the workspace is a status word: 0, or 1 + the index of a segment with out-of-range tables. */
+size_t  i2v_det_eval_match_workspace_bytes(int32_t n_det);
+int32_t i2v_det_eval_match(const int32_t* seg_det_off, const int32_t* seg_gt, const int32_t* gt_off,
+                           const int32_t* det_key, const double* det_box, const double* gt_box, const int32_t* gt_hard,
+                           int32_t n_seg, int32_t n_det, int32_t n_slots, int32_t n_gt, int32_t max_gt, double ovthresh,
+                           int32_t* flag, double* ovmax, int32_t* jmax,
+                           void* workspace, size_t workspace_bytes, void* stream);
+/* Per class c (detections [cls_off[c], cls_off[c+1]), n_cls <= 255, fewer than 2^24 in one class): perm = the
+ * detections in descending key, equal keys in results-file order (a stable sort); along it cum_tp / cum_fp (inclusive
+ * integer sums of the flags), rec = cum_tp / npos[c] and prec = cum_tp / max(cum_tp + cum_fp, eps) in fp64 (all n_det,
+ * at the class's own offsets); ap_area (n_cls) = the area under the precision envelope, its terms added in index
+ * order; ap_11pt (n_cls) = the 11-point mean of the 2007 devkit.  npos[c] == 0 gives nan rec and a nan ap_area, as the
+ * reference's division does.  Status word: 0, or 1 + the index of a class whose table entries are out of range. */
+size_t  i2v_det_eval_curve_workspace_bytes(int32_t n_det);
+int32_t i2v_det_eval_curve(const int32_t* det_key, const int32_t* cls_off, const int32_t* flag, const int32_t* npos,
+                           int32_t n_cls, int32_t n_det, int32_t* perm, int32_t* cum_tp, int32_t* cum_fp,
+                           double* rec, double* prec, double* ap_area, double* ap_11pt,
+                           void* workspace, size_t workspace_bytes, void* stream);
+
 /* IoU of boxes (B,N,4 | stride_box floats per row, first 4 used after `box_off`) against
  * gt (B,K,5): bbox_transform.py:168-257 (bbox_overlaps_batch) incl. the zero-area
  * masks; also emits per-row max/argmax (first max).  overlaps may be NULL. */

@@ -8,7 +8,7 @@ regenerate).
 
 Two tiers, recorded per file in the ``tier`` field:
   "direct"       the reference module imports as shipped (sys.path only):
-                 rpn/generate_anchors.py, rpn/bbox_transform.py, nms/nms_cpu.py
+                 rpn/generate_anchors.py, rpn/bbox_transform.py, nms/nms_cpu.py, datasets/voc_eval.py (by path)
   "extracted"    roi_align/src/roi_align.c:80-136 ``ROIAlignForwardCpu``: the file as a whole needs <TH/TH.h> (its
                  THFloatTensor wrappers), the function itself only <math.h>; oracle/build_ref.py pipes the function's
                  own text to gcc unmodified (no stand-in header, nothing of it written to disk but the .so)
@@ -870,13 +870,247 @@ def gen_video():
          margin_ov_gap=np.float64(st.get("ov_gap", np.inf)))
 
 
+# ----------------------------------------------------------------------------- detection evaluation (VOC AP)
+def det_eval_fixture_inputs(seed=4100, n_images=240, n_classes=9):
+    """The seeded detections and annotations of tests/golden/det_eval.npz: (all_boxes, roidb, classes).  Ground-truth boxes
+    are integers (the XML holds integers); detection coordinates lie on a quarter-pixel grid (halves of the '%.1f' included)
+    and the quantised scores of a class are pairwise distinct.  Class ``n_classes - 2`` has no detections, class
+    ``n_classes - 1`` detections but no ground truth."""
+    rng = np.random.default_rng(seed)
+    classes = tuple(["__background__"] + ["kind%d" % c for c in range(1, n_classes)])
+    no_det, no_gt = n_classes - 2, n_classes - 1
+    gts = [[] for _ in range(n_images)]                  # rows x1 y1 x2 y2 cls hard
+    dets = [[[] for _ in range(n_images)] for _ in range(n_classes)]      # rows x1 y1 x2 y2 (score comes later)
+
+    def rand_box(lo=24, hi=200):
+        w, h = rng.integers(lo, hi, 2)
+        x, y = rng.integers(0, 700 - w), rng.integers(300, 900 - h)
+        return [int(x), int(y), int(x + w), int(y + h)]
+
+    for i in range(8, n_images):                         # the generic part (images 0-7 hold the constructions)
+        for _ in range(int(rng.integers(0, 9))):
+            c = int(rng.integers(1, no_gt))              # classes 1 .. no_det have ground truth
+            b = rand_box()
+            gts[i].append(b + [c, int(rng.random() < 0.15)])
+            if c == no_det:
+                continue
+            for _ in range(int(rng.choice([0, 1, 1, 1, 2, 3]))):          # detections near it; several: duplicates
+                jit = rng.integers(-40, 41, 4) / 4.0 * (1.0 if rng.random() < 0.7 else 4.0)
+                d = np.asarray(b, np.float64) + jit
+                dets[c][i].append([min(d[0], d[2]), min(d[1], d[3]), max(d[0], d[2]), max(d[1], d[3])])
+        for _ in range(int(rng.integers(0, 4))):         # detections of anything anywhere
+            c = int(rng.choice([k for k in range(1, n_classes) if k != no_det]))
+            b = np.asarray(rand_box(), np.float64) + rng.integers(0, 4, 4) / 4.0
+            dets[c][i].append(b.tolist())
+    # image 0, class 1: a duplicate of a claimed ground truth; best claimed while the second best is free
+    gts[0] += [[10, 10, 60, 60, 1, 0], [14, 10, 64, 60, 1, 0]]
+    dets[1][0] += [[10, 10, 60, 60], [11, 10, 61, 60], [10.25, 10.5, 60, 59.75]]
+    # image 0, class 2: two identical ground truths (the first wins), then a second detection that finds the first claimed
+    gts[0] += [[100, 100, 150, 150, 2, 0], [100, 100, 150, 150, 2, 0]]
+    dets[2][0] += [[100, 100, 150, 150], [100.5, 100, 150, 150.5]]
+    # image 1, class 3: the best match is hard, and it is the best-scored detection of the class
+    gts[1] += [[200, 200, 260, 260, 3, 1], [300, 200, 360, 260, 3, 0]]
+    dets[3][1] += [[200, 200, 260, 260], [300.5, 200.5, 360, 260]]
+    # image 2, class 4: an overlap of exactly 0.5 -- [1,1,10,10] against [1,1,10,5] in the file's coordinates
+    gts[2] += [[0, 0, 9, 4, 4, 0]]
+    dets[4][2] += [[0, 0, 9, 9]]
+    # image 3, class 5: 80 ground truths in one image, detections on most of them
+    for r in range(8):
+        for q in range(10):
+            b = [20 + 60 * q, 20 + 60 * r, 60 + 60 * q, 60 + 60 * r]
+            gts[3].append(b + [5, int((r * 10 + q) % 17 == 5)])
+            if (r * 10 + q) % 5 != 2:
+                dets[5][3].append((np.asarray(b, np.float64) + rng.integers(-12, 13, 4) / 4.0).tolist())
+    dets[5][3].append([20 + 60 * 7, 20 + 60 * 6, 60 + 60 * 7, 60 + 60 * 6])       # index 67 > 63, exact
+    # image 4: detections of class 1 in an image that has none of its ground truth
+    gts[4] += [[50, 50, 120, 120, 2, 0]]
+    dets[1][4] += [[50, 50, 120, 120], [300.75, 310.25, 400.5, 420]]
+    # scores: distinct thousandths within a class, off the grid by less than half a step; the constructions' first
+    # detections get the class's best scores in the order listed
+    special = {1: [(0, 0), (0, 1), (0, 2)], 2: [(0, 0), (0, 1)], 3: [(1, 0), (1, 1)]}
+    all_boxes = [[np.zeros((0, 5), np.float32) for _ in range(n_images)] for _ in range(n_classes)]
+    for c in range(1, n_classes):
+        where = [(i, k) for i in range(n_images) for k in range(len(dets[c][i]))]
+        assert len(where) < 990, (c, len(where))
+        first = [w for w in special.get(c, []) if w in where]
+        rest = [w for w in where if w not in first]
+        rest = [rest[j] for j in rng.permutation(len(rest))]
+        keys = np.sort(rng.permutation(np.arange(1, 1000))[:len(where)])[::-1]
+        score = {}
+        for key, w in zip(keys, first + rest):
+            score[w] = np.float32((key + rng.uniform(-0.4, 0.4)) / 1000.0)
+        for i in range(n_images):
+            if dets[c][i]:
+                rows = [list(dets[c][i][k]) + [score[(i, k)]] for k in range(len(dets[c][i]))]
+                all_boxes[c][i] = np.asarray(rows, np.float64).astype(np.float32)
+    roidb = []
+    for i in range(n_images):
+        g = np.asarray(gts[i], np.int64).reshape(-1, 6)
+        roidb.append({"boxes": g[:, :4].astype(np.uint16), "gt_classes": g[:, 4].astype(np.int32),
+                      "gt_ishard": g[:, 5].astype(np.int32)})
+    return all_boxes, roidb, classes
+
+
+def _write_voc_files(tmp, all_boxes, roidb, classes):
+    """What the reference's evaluation reads: the image-set file, one minimal XML per image (boxes + 1, difficult,
+    truncated) and one results file per class in the writer's own line format (_write_voc_results_file).  Returns the
+    image-set file; the results of class ``name`` are ``tmp/det_<name>.txt``, the annotations ``tmp/Annotations/<id>.xml``."""
+    os.makedirs(os.path.join(tmp, "Annotations"))
+    names = ["%06d" % i for i in range(len(roidb))]
+    setfile = os.path.join(tmp, "test.txt")
+    with open(setfile, "w") as f:
+        f.write("".join(n + "\n" for n in names))
+    for i, e in enumerate(roidb):
+        objs = "".join("<object><name>%s</name><truncated>0</truncated><difficult>%d</difficult><bndbox><xmin>%d</xmin>"
+                       "<ymin>%d</ymin><xmax>%d</xmax><ymax>%d</ymax></bndbox></object>"
+                       % ((classes[cl], hard) + tuple(int(v) + 1 for v in bx))
+                       for bx, cl, hard in zip(e["boxes"], e["gt_classes"], e["gt_ishard"]))
+        with open(os.path.join(tmp, "Annotations", names[i] + ".xml"), "w") as f:
+            f.write("<annotation>%s</annotation>" % objs)
+    for c in range(1, len(classes)):
+        with open(os.path.join(tmp, "det_%s.txt" % classes[c]), "wt") as f:
+            for i in range(len(roidb)):
+                d = all_boxes[c][i]
+                for k in range(d.shape[0]):
+                    f.write('{:s} {:.3f} {:.1f} {:.1f} {:.1f} {:.1f}\n'.format(names[i], d[k, -1], d[k, 0] + 1, d[k, 1] + 1,
+                                                                              d[k, 2] + 1, d[k, 3] + 1))
+    return setfile
+
+
+def _load_voc_eval():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("ref_voc_eval", os.path.join(REF, "lib", "datasets", "voc_eval.py"))
+    ref = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(ref)
+    return ref
+
+
+def time_det_eval(n_images=2400):
+    """Orientation for profiles/r10_det_eval.txt: the reference's voc_eval on this machine's CPU on the seeded set of
+    tests/det_eval_golden.py fresh_set (files written first, annotations parsed and cached before the clock starts)."""
+    import contextlib
+    import io
+    import tempfile
+    import time
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import det_eval_golden as dg
+    ref = _load_voc_eval()
+    all_boxes, roidb, classes = dg.fresh_set(n_images=n_images)
+    with tempfile.TemporaryDirectory() as tmp:
+        t0 = time.perf_counter()
+        setfile = _write_voc_files(tmp, all_boxes, roidb, classes)
+        print("  reference writer format, %d images: files written in %.1f s" % (n_images, time.perf_counter() - t0))
+        total, n_det = 0.0, 0
+        for c in range(1, len(classes)):
+            args = (os.path.join(tmp, "det_%s.txt" % classes[c]), os.path.join(tmp, "Annotations", "{:s}.xml"), setfile, classes[c],
+                    os.path.join(tmp, "cache"))
+            if c == 1:
+                with contextlib.redirect_stdout(io.StringIO()), np.errstate(all="ignore"):
+                    t0 = time.perf_counter()
+                    ref.voc_eval(*args)                  # parses the XML and writes the cache
+                    print_later = time.perf_counter() - t0
+            with contextlib.redirect_stdout(io.StringIO()), np.errstate(all="ignore"):
+                t0 = time.perf_counter()
+                rec, prec, ap = ref.voc_eval(*args)
+                dt = time.perf_counter() - t0
+            total += dt
+            n_det += len(rec)
+            print("  voc_eval %-8s %7d detections %8.2f s   ap %.4f" % (classes[c], len(rec), dt, ap))
+        print("  first call with the XML parse: %.1f s; voc_eval over all classes, annotations cached: %.1f s for %d detections "
+              "(%.1f us per detection)" % (print_later, total, n_det, 1e6 * total / max(n_det, 1)))
+
+
+def gen_det_eval():
+    """tests/golden/det_eval.npz: the reference's own ``voc_eval`` (lib/datasets/voc_eval.py, loaded by path, unmodified) on
+    seeded detections written in its results-file format and annotations written as minimal VOC XML, per class, both AP
+    forms, at two overlap thresholds.  The file holds the inputs and rec / prec / ap."""
+    import contextlib
+    import io
+    import tempfile
+    from i2vsgg_amd import detection_eval as de
+    ref = _load_voc_eval()
+    all_boxes, roidb, classes = det_eval_fixture_inputs()
+    C, I = len(classes) - 1, len(roidb)
+    thresholds = (0.5, 0.7)
+    # --- the conditions the fixture must meet
+    pk = de.pack(all_boxes, roidb, len(classes))
+    for k in range(C):
+        keys = pk.det_key[pk.cls_off[k]:pk.cls_off[k + 1]]
+        assert len(np.unique(keys)) == len(keys), "quantised scores of class %d tie" % (k + 1)
+    for c in range(1, C + 1):
+        for d in all_boxes[c]:
+            if len(d):
+                xy = d[:, :4].astype(np.float64)
+                assert (xy * 4 == np.round(xy * 4)).all() and (np.abs(xy) < 2 ** 20).all()
+                assert ((d[:, :4] + np.float32(1)).astype(np.float64) == xy + 1.0).all()
+    flag, ovmax, jmax = de.match_arrays_host(pk, 0.5)
+    n_per = np.diff(pk.cls_off)
+    assert (n_per == 0).any() and ((n_per > 0) & (pk.npos == 0)).any()                   # no detections; detections, npos 0
+    seg_ng = np.diff(pk.gt_off)[pk.seg_gt]
+    assert (seg_ng == 0).any() and (seg_ng > 64).any()
+    big = np.nonzero(seg_ng > 64)[0][0]
+    assert (jmax[pk.seg_det_off[big]:pk.seg_det_off[big + 1]] > 63).any()
+    assert (ovmax == 0.5).any() and (flag[ovmax == 0.5] == de.FP).all()
+    have = dict(dup=False, second_free=False, twin=False, hard_first=False)
+    for s in range(len(pk.seg_gt)):
+        d0, d1 = pk.seg_det_off[s], pk.seg_det_off[s + 1]
+        g0, g1 = pk.gt_off[pk.seg_gt[s]], pk.gt_off[pk.seg_gt[s] + 1]
+        if g1 == g0:
+            continue
+        ov = de._overlaps(pk.det_box[d0:d1], pk.gt_box[g0:g1])
+        claimed = set(jmax[d0:d1][flag[d0:d1] == de.TP].tolist())
+        for q in range(d1 - d0):
+            j = jmax[d0 + q]
+            if flag[d0 + q] == de.FP and ovmax[d0 + q] > 0.5 and not pk.gt_hard[g0 + j]:
+                have["dup"] = True
+                free = [g for g in range(g1 - g0) if g != j and ov[q, g] > 0.5 and g not in claimed and not pk.gt_hard[g0 + g]]
+                have["second_free"] |= bool(free)
+            if (ov[q] == ov[q, j]).sum() > 1 and (pk.gt_box[g0:g1][ov[q] == ov[q, j]] == pk.gt_box[g0 + j]).all() and flag[d0 + q] == de.TP:
+                have["twin"] = True
+    for k in range(C):
+        a, b = pk.cls_off[k], pk.cls_off[k + 1]
+        if b > a and flag[a + np.argmax(pk.det_key[a:b])] == de.IGNORED:
+            have["hard_first"] = True
+    assert all(have.values()), have
+    assert (flag == de.IGNORED).sum() > 1
+    # --- the reference's files and its own evaluation
+    out = {}
+    with tempfile.TemporaryDirectory() as tmp:
+        setfile = _write_voc_files(tmp, all_boxes, roidb, classes)
+        for ti, thr in enumerate(thresholds):
+            recs, precs = [], []
+            ap = np.zeros((2, C), np.float64)
+            for c in range(1, C + 1):
+                for m, use07 in enumerate((False, True)):
+                    with contextlib.redirect_stdout(io.StringIO()), np.errstate(all="ignore"):
+                        rec, prec, a = ref.voc_eval(os.path.join(tmp, "det_%s.txt" % classes[c]),
+                                                    os.path.join(tmp, "Annotations", "{:s}.xml"), setfile, classes[c],
+                                                    os.path.join(tmp, "cache"), ovthresh=thr, use_07_metric=use07)
+                    ap[m, c - 1] = a
+                recs.append(np.asarray(rec, np.float64))
+                precs.append(np.asarray(prec, np.float64))
+                assert len(rec) == n_per[c - 1]
+            out["rec_%d" % ti], out["prec_%d" % ti] = np.concatenate(recs), np.concatenate(precs)
+            out["ap_area_%d" % ti], out["ap_11pt_%d" % ti] = ap[0], ap[1]
+            print("    ovthresh %.1f  ap %s" % (thr, np.array2string(ap[0], precision=4)))
+    det = np.concatenate([d for c in range(1, C + 1) for d in all_boxes[c] if len(d)]).astype(np.float32)
+    det_cls = np.concatenate([np.full(len(d), c, np.int32) for c in range(1, C + 1) for d in all_boxes[c] if len(d)])
+    det_img = np.concatenate([np.full(len(d), i, np.int32) for c in range(1, C + 1) for i, d in enumerate(all_boxes[c]) if len(d)])
+    gt_img = np.concatenate([np.full(len(e["boxes"]), i, np.int32) for i, e in enumerate(roidb)])
+    save("det_eval", "direct", thresholds=np.asarray(thresholds, np.float64), classes=np.array(classes), n_images=np.int32(I),
+         det=det, det_cls=det_cls, det_img=det_img, gt_img=gt_img,
+         gt_box=np.concatenate([e["boxes"] for e in roidb]).astype(np.int32),
+         gt_cls=np.concatenate([e["gt_classes"] for e in roidb]).astype(np.int32),
+         gt_hard=np.concatenate([e["gt_ishard"] for e in roidb]).astype(np.int32), npos=pk.npos, **out)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--only", default="")
     a = ap.parse_args()
     os.makedirs(GOLD, exist_ok=True)
     todo = a.only.split(",") if a.only else ["direct", "roialign", "roialign_fresh", "tails", "rpn", "nets", "full", "ctx", "step",
-                                             "vrd", "video"]
+                                             "vrd", "video", "det_eval"]
     if "direct" in todo:
         print("[direct imports]")
         gen_direct()
@@ -889,6 +1123,12 @@ def main():
     if "tails" in todo:
         print("[eval tails: direct imports + detection_output compiled from its own lines]")
         gen_eval_tails()
+    if "det_eval" in todo:
+        print("[detection evaluation: lib/datasets/voc_eval.py imported as shipped]")
+        gen_det_eval()
+    if "det_eval_time" in todo:
+        print("[the reference's voc_eval, timed on this CPU]")
+        time_det_eval()
     if "video" in todo:
         print("[video association / evaluation: lib/utils.py functions compiled from their own lines]")
         gen_video()
