@@ -1,6 +1,6 @@
 """Video relations without a GPU: the host implementation of i2vsgg_amd.video against the reference's association() and
-evaluate() (tests/golden/video_association.npz, video_eval.npz; tools/gen_golden.py --only video), the host pre-pass, the
-argument validation of the new C entry points."""
+evaluate() (tests/golden/video_association.npz, video_eval.npz, video_eval_edges.npz; tools/gen_golden.py --only video), the
+host pre-pass, the argument validation of the new C entry points."""
 import copy
 import ctypes
 
@@ -74,6 +74,34 @@ def test_host_evaluation_matches_the_reference(reference):
     record_margin("test_host_evaluation_matches_the_reference", "largest metric difference", np.abs(got - g["metrics"]).max(), 1e-6)
     assert np.abs(got - g["metrics"]).max() <= 1e-6
     assert 0 < g["metrics"][0] < 1
+
+
+@pytest.fixture(scope="module")
+def edge_set():
+    return vg.eval_edge_set(vg.EDGE_SEED, grid=True, clamped=False)
+
+
+def test_host_evaluation_matches_the_reference_on_the_edges(edge_set):
+    """tests/golden/video_eval_edges.npz (tools/gen_golden.py --only video_edges): the reference on a set with 150 ground
+    truths in one video, duplicate annotations, tied scores and overlaps exactly on the threshold, at thresholds 0.5 and 0."""
+    from i2vsgg_amd import video
+    name = "test_host_evaluation_matches_the_reference_on_the_edges"
+    g = golden("video_eval_edges")
+    assert int(g["seed"]) == vg.EDGE_SEED
+    pred, gts = edge_set
+    for tag, thr in (("50", 0.5), ("00", 0.0)):
+        pe, ov, hit, hit_ov = video.match(pred, gts, thr, device=None)
+        vg.assert_edge_golden(g, tag, pe, ov, hit, video.evaluate(pred, gts, thr, device=None), name, record_margin)
+    # worked by hand: 100 / (100 + 200 - 100), 300 / (300 + 400 - 300), touching durations
+    pe, ov, hit, hit_ov = video.match(pred, gts, 0.5, device=None)
+    p0 = vg.edge_rows(pe, "exact")
+    assert ov[p0, 0] == 0.5 and hit[p0] == 0 and hit_ov[p0] == 0.5
+    assert ov[p0 + 1, 1] == 0.75 and hit[p0 + 1] == 1
+    assert ov[p0 + 2, 2] == 0.0 and hit[p0 + 2] == -1 and hit_ov[p0 + 2] == -1.0
+    pe, ov, hit, hit_ov = video.match(pred, gts, 0.0, device=None)
+    assert hit[p0 + 2] == 2 and hit_ov[p0 + 2] == 0.0
+    pe, ov, hit, hit_ov = video.match(pred, gts, 0.75, device=None)
+    assert hit[p0] == -1 and hit[p0 + 1] == 1 and hit_ov[p0 + 1] == 0.75
 
 
 def test_voc_ap_both_forms():

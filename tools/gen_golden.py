@@ -870,6 +870,60 @@ def gen_video():
          margin_ov_gap=np.float64(st.get("ov_gap", np.inf)))
 
 
+def gen_video_edges():
+    """tests/golden/video_eval_edges.npz: the reference's eval_detection_scores / viou / evaluate on
+    tests/video_golden.py eval_edge_set(EDGE_SEED, grid=True, clamped=False) -- more than 64 and 128 ground truths, duplicate
+    annotations, tied scores, overlaps exactly on the threshold -- at thresholds 0.5 and 0.0.  Per threshold: which
+    predictions (packed order) are true positives, the overlaps the reference computed (flat cell index into the
+    (n_pred, max_gt) table, value) and the six metrics.  The reference raises on a trajectory shorter than its duration,
+    so the ``clamped`` video stays out."""
+    import json
+    import tempfile
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import video_golden as vg
+    from i2vsgg_amd import video
+    ns = _utils_functions(["voc_ap", "viou", "eval_detection_scores", "eval_tagging_scores", "evaluate"])
+    predictions, gts = vg.eval_edge_set(vg.EDGE_SEED, grid=True, clamped=False)
+    ref_viou = ns["viou"]
+    calls = []
+    ns["viou"] = lambda t1, d1, t2, d2: calls.append((id(t1), id(t2), ref_viou(t1, d1, t2, d2))) or calls[-1][2]
+    out = {}
+    for tag, thr in (("50", 0.5), ("00", 0.0)):
+        pe, ov_h, hit_h, _ = video.match(predictions, gts, thr)
+        tp_ref = np.zeros(len(hit_h), bool)
+        cell, val = [], []
+        for v, vid in enumerate(pe.vids):
+            preds, g = predictions.get(vid, []), gts[vid]
+            pid = dict((id(r[key]), (k, c)) for k, r in enumerate(preds) for c, key in enumerate(("sub_traj", "obj_traj")))
+            gid = dict((id(r[key]), (k, c)) for k, r in enumerate(g) for c, key in enumerate(("sub_traj", "obj_traj")))
+            del calls[:]
+            _, _, hit_scores = ns["eval_detection_scores"](g, preds, thr)
+            order = np.argsort(-np.array([r["score"] for r in preds]), kind="stable")
+            p0 = int(pe.pred_off[v])
+            tp_ref[p0 + order] = np.isfinite(hit_scores)
+            for (a, b, x), (a2, b2, x2) in zip(calls[0::2], calls[1::2]):
+                assert pid[a][0] == pid[a2][0] and gid[b][0] == gid[b2][0] and pid[a][1] == 0 and pid[a2][1] == 1
+                cell.append((p0 + pid[a][0]) * ov_h.shape[1] + gid[b][0])
+                val.append(min(x, x2))
+        cell, val = np.asarray(cell, np.int32), np.asarray(val, np.float64)
+        # the package's host form must already agree: equal true positives, and on this grid equal bits
+        assert ((hit_h >= 0) == tp_ref).all()
+        assert (ov_h.reshape(-1)[cell] == val).all()
+        with tempfile.NamedTemporaryFile("w", suffix=".json", delete=False) as f:
+            json.dump(gts, f)
+        try:
+            mean_ap, rec, mprec = ns["evaluate"](predictions, f.name, thr)
+        finally:
+            os.unlink(f.name)
+        print("    threshold %.1f: %d of %d true positives, %d overlaps; mAP %.6f  R@50 %.6f  R@100 %.6f  P@1 %.6f  P@5 %.6f  P@10 %.6f"
+              % (thr, tp_ref.sum(), len(tp_ref), len(cell), mean_ap, rec[50], rec[100], mprec[1], mprec[5], mprec[10]))
+        out["tp_" + tag], out["ov_cell_" + tag], out["ov_" + tag] = tp_ref, cell, val
+        out["metrics_" + tag] = np.array([mean_ap, rec[50], rec[100], mprec[1], mprec[5], mprec[10]], np.float64)
+    assert out["tp_00"].sum() > out["tp_50"].sum() and (out["ov_00"] == 0.0).any() and (out["ov_50"] == 0.5).any()
+    save("video_eval_edges", "extracted", seed=np.int32(vg.EDGE_SEED), vids=np.array(pe.vids), pred_off=pe.pred_off,
+         max_gt=np.int32(ov_h.shape[1]), thresholds=np.array([0.5, 0.0]), **out)
+
+
 # ----------------------------------------------------------------------------- detection evaluation (VOC AP)
 def det_eval_fixture_inputs(seed=4100, n_images=240, n_classes=9):
     """The seeded detections and annotations of tests/golden/det_eval.npz: (all_boxes, roidb, classes).  Ground-truth boxes
@@ -1132,6 +1186,9 @@ def main():
     if "video" in todo:
         print("[video association / evaluation: lib/utils.py functions compiled from their own lines]")
         gen_video()
+    if "video" in todo or "video_edges" in todo:
+        print("[video evaluation on the edge set: the same lib/utils.py functions]")
+        gen_video_edges()
     if any(t in todo for t in ("rpn", "nets", "full", "vrd", "ctx", "step")):
         print("[imports with placeholders]")
         cfg = install_placeholders()
