@@ -60,11 +60,15 @@ __global__ void rpn_decode_kernel(const float* __restrict__ cls, int is_prob, co
 // ------------------------------------------------------------------ bitonic sort
 // key = (order-preserving u32 of the score) << 32 | (0xFFFFFFFF - index): sorting keys
 // DESCENDING gives descending score with ascending index on ties; padding keys are 0.
+// -0.0f is mapped as +0.0f, so the two zeros tie as they do in an IEEE comparison (their bit
+// patterns alone would rank every +0.0 ahead of every -0.0).  NaN keys land wherever their bits
+// put them: their order is unspecified.
 constexpr int SORT_TILE = 4096;     // u64 keys per LDS tile (32 KiB)
 constexpr int SORT_THREADS = 512;
 
 __device__ inline unsigned int f2ord(float f) {
     unsigned int u = __float_as_uint(f);
+    if (u == 0x80000000u) u = 0u;
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 

@@ -160,6 +160,9 @@ int32_t i2v_rpn_proposal(const float* cls, int32_t is_prob, const float* bbox, c
 int32_t i2v_rpn_decode(const float* cls, int32_t is_prob, const float* bbox, const float* im_info,
                        const float* base_anchors, int32_t B, int32_t H, int32_t W, int32_t A, int32_t feat_stride,
                        float* proposals /* (B,HWA,4) */, float* scores /* (B,HWA) */, void* stream);
+/* i2v_sort_desc: order_out[s][r] = index of the r-th largest key of segment s; n <= 2^24.  Equal keys come in
+ * ascending index (a stable descending sort).  +0.0 and -0.0 are equal, as in an IEEE comparison; +-inf and denormals
+ * order by value.  Keys must be NaN-free: where a NaN lands is unspecified. */
 size_t  i2v_sort_desc_workspace_bytes(int32_t n_seg, int32_t n);
 int32_t i2v_sort_desc(const float* keys, int32_t n_seg, int32_t n, int32_t* order_out /* (n_seg,n) */,
                       void* workspace, size_t workspace_bytes, void* stream);
