@@ -1272,7 +1272,7 @@ int run_conv(ConvP p, hipStream_t st, void* split_ws = nullptr, size_t split_ws_
     // round 5: the ordered finish takes ANY number of splits (rounds of kSplitInKernelMax) and any output size, so that no
     // forward or data-gradient GEMM of the relation head depends on arrival order (SPLIT_ATOMICS = 2 restores round 4's rule
     // everywhere: atomics beyond four splits and for outputs under 2^18 elements; 1: atomics always)
-    // SPLIT_ATOMICS == 0 (what the relation step's head context selects, ops.LaunchContext(ordered=True)): ordered for every
+    // SPLIT_ATOMICS == 0 (what the relation step's head context selects, launch.LaunchContext(ordered=True)): ordered for every
     // shape.  The process default is 2, round 4's rule: measured on configs[2], ordering every reduction of the step -- its
     // 8-16-way filter-gradient splits, the bias sums of netD_style's 37500-row projections -- costs 46.2 -> 48.1 ms.
     const bool r4_ok = p.splitk <= kSplitInKernelMax && (long long)p.M * p.N >= (1 << 18);

@@ -13,7 +13,7 @@
 import numpy as np
 import torch
 
-from . import ops
+from . import launch, ops
 from .graphs import GraphRecorder, replay_graph
 from .model.utils.config import cfg
 
@@ -25,7 +25,7 @@ class _FrameShape:
         n, h, w = key
         self.key = key
         self.im = torch.zeros((n, 4, h, w), device=device).contiguous(memory_format=torch.channels_last)
-        self.ctx = [ops.LaunchContext(device) for _ in range(n)]
+        self.ctx = [launch.LaunchContext(device) for _ in range(n)]
         self.graph = None             # None: not captured yet; False: capture failed (eager launches for this size)
         self.tick = 0
 
@@ -40,7 +40,7 @@ class _FrameGraphStep(GraphRecorder):
             raise RuntimeError("%s: the network must be in eval mode (test_net_...:131 fasterRCNN.eval())" % type(self).__name__)
         self.net, self.dev, self.frames = net, torch.device(device), int(frames)
         self.use_graph, self.max_graphs = bool(use_graph), max(int(max_graphs), 1)
-        self._streams = [ops.role_stream(self.dev, ("frame", f)) for f in range(self.frames)]
+        self._streams = [launch.role_stream(self.dev, ("frame", f)) for f in range(self.frames)]
         self.shapes, self._pool, self._tick, self._staged = {}, None, 0, None
         self.graph_error = None
         self._slot = 0
@@ -49,9 +49,9 @@ class _FrameGraphStep(GraphRecorder):
     def _body(self, fs):
         main = torch.cuda.current_stream(self.dev)
         for f, st in enumerate(self._streams):     # fork from the launching stream itself (a fork inside a fork breaks capture)
-            with ops.branch(st, main):
+            with launch.branch(st, main):
                 self._frame(fs, f)
-        ops.join(main, *self._streams)
+        launch.join(main, *self._streams)
 
     def _shape(self, H, W):
         key = (self.frames, int(H), int(W))

@@ -6,7 +6,7 @@ import gc
 
 import torch
 
-from . import ops, parallel
+from . import launch, parallel
 
 
 _REPLAY_STREAMS = {}
@@ -30,7 +30,7 @@ def replay_graph(graph, device=None):
         return
     s = _REPLAY_STREAMS.get(dev.index)
     if s is None:
-        s = _REPLAY_STREAMS[dev.index] = ops.role_stream(dev, "replay")
+        s = _REPLAY_STREAMS[dev.index] = launch.role_stream(dev, "replay")
     s.wait_stream(cur)
     with torch.cuda.stream(s):
         graph.replay()
@@ -56,7 +56,7 @@ class GraphRecorder:
             return g
         except Exception as e:      # report; the caller keeps the eager form
             self.graph_error = repr(e)
-            ops.reset_branches()
+            launch.reset_branches()
             torch.cuda.synchronize(self.dev)
             return False
 
@@ -110,7 +110,7 @@ class CapturedStep(GraphRecorder):
         """``n`` eager ``body()`` calls on the "warmup" role stream, ordered behind the caller's stream and joined back into it;
         ``after_first()`` right behind the first one (arenas are sized by what it launched); the device is idle afterwards."""
         cur = torch.cuda.current_stream(self.dev)
-        s = ops.role_stream(self.dev, "warmup")
+        s = launch.role_stream(self.dev, "warmup")
         s.wait_stream(cur)
         with torch.cuda.stream(s):
             for i in range(n):
@@ -126,6 +126,6 @@ class CapturedStep(GraphRecorder):
             return self._step()
         except BaseException:
             # an eager body that raised between a branch and its join leaves process-wide role streams marked open
-            # (ops._FORKED): every later step object on this device would be refused its branches
-            ops.reset_branches()
+            # (launch.open_branches()): every later step object on this device would be refused its branches
+            launch.reset_branches()
             raise

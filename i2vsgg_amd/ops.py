@@ -7,14 +7,15 @@ Conventions
   * conv weights keep the reference's logical shape (Cout,Cin,KH,KW), also channels_last,
     which is exactly the (Cout,KH,KW,Cin) K-major filter layout of the implicit GEMM;
   * every function launches on torch's current stream and never synchronises;
+  * scratch, the split-K workspace and pre-zeroed outputs come from the current ``launch.LaunchContext`` (``launch.py``
+    owns them, the role streams and the graph branches; nothing here decides which buffer a launch may touch);
   * no CPU fallback: non-CUDA tensors raise.
 """
-import os
 
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, launch
 from ._lib import (EPI_BIAS, EPI_RELU, EPI_RESIDUAL, EPI_SCALE, EPI_ZEROED, LAYOUT_NCHW, LAYOUT_NHWC, check, lib, ptr,
                    stream)
 
@@ -39,26 +40,6 @@ def as_nhwc(x):
 
 def _is_nhwc(x):
     return x.dim() == 4 and x.is_contiguous(memory_format=_CL)
-
-
-_ws_cache = {}
-SCRATCH = None      # dict of the active LaunchContext (below); None -> scratch per launch stream
-
-
-def workspace(nbytes, device, tag="default"):
-    """Grow-only scratch buffer per (tag, owner).  The owner is the active ``LaunchContext`` when a step object has
-    installed one, else the launch stream: two pieces of work that may run concurrently on the device (two streams, two
-    HIP graphs replayed side by side) never share a scratch buffer -- every kernel that uses one assumes that the
-    launches before it on ITS stream are the only other users."""
-    cache = SCRATCH
-    if cache is None:
-        key = (device.index if device.index is not None else torch.cuda.current_device(), stream())
-        cache = _ws_cache.setdefault(key, {})
-    buf = cache.get(tag)
-    if buf is None or buf.numel() < nbytes:
-        buf = torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=device)
-        cache[tag] = buf
-    return buf
 
 
 # ----------------------------------------------------------------------------- ROI ops
@@ -109,7 +90,8 @@ class _RoIAlignFn(torch.autograd.Function):
             return gfeat, None, None, None, None, None, None
         # the scatter accumulates with atomics into zeros: inside a step they come from the step's pre-zeroed arena (one
         # clear per step for every atomically accumulated output) instead of a fill kernel of their own
-        gfeat = ARENA.take(B, C, H, W) if (ARENA is not None and nhwc) else None
+        arena = launch.arena()
+        gfeat = arena.take(B, C, H, W) if (arena is not None and nhwc) else None
         if gfeat is None:
             gfeat = torch.empty(shape, device=gout.device, dtype=torch.float32,
                                 memory_format=_CL if nhwc else torch.contiguous_format).zero_()
@@ -256,7 +238,7 @@ def nms_sorted(dets, thresh, max_keep=0):
     keep = torch.empty((n_img, max(n, 1)), device=d.device, dtype=torch.int32)
     num = torch.empty((n_img,), device=d.device, dtype=torch.int32)
     nb = lib.i2v_nms_workspace_bytes(n_img, n)
-    ws = workspace(nb, d.device, "nms")
+    ws = launch.workspace(nb, d.device, "nms")
     check(lib.i2v_nms_sorted(ptr(d), n_img, n, float(thresh), int(max_keep), ptr(keep), ptr(num), ptr(ws), ws.numel(),
                              stream()), "nms_sorted")
     return keep, num
@@ -270,7 +252,7 @@ def sort_desc(keys):
         k = k.unsqueeze(0)
     n_seg, n = k.shape
     order = torch.empty((n_seg, n), device=k.device, dtype=torch.int32)
-    ws = workspace(lib.i2v_sort_desc_workspace_bytes(n_seg, n), k.device, "sort")
+    ws = launch.workspace(lib.i2v_sort_desc_workspace_bytes(n_seg, n), k.device, "sort")
     check(lib.i2v_sort_desc(ptr(k), n_seg, n, ptr(order), ptr(ws), ws.numel(), stream()), "sort_desc")
     return order
 
@@ -301,7 +283,7 @@ def rpn_proposal(cls_nhwc, bbox_nhwc, im_info, base_anchors, feat_stride, pre_nm
     kept = torch.empty((B, post_nms_top_n), device=dev, dtype=torch.int32) if want_index else None
     num = torch.empty((B,), device=dev, dtype=torch.int32) if want_index else None
     nb = lib.i2v_rpn_proposal_workspace_bytes(B, H, W, A, int(pre_nms_top_n))
-    ws = workspace(nb, dev, "rpn")
+    ws = launch.workspace(nb, dev, "rpn")
     info = im_info.contiguous().float()
     base = base_anchors.contiguous().float()
     check(lib.i2v_rpn_proposal(ptr(cls_nhwc), int(is_prob), ptr(bbox_nhwc), ptr(info), ptr(base), B, H, W, A,
@@ -352,48 +334,6 @@ class _Timed:
             PROFILE.append(self.rec)
 
 
-class ZeroArena:
-    """Pre-zeroed output arena for the split-K convolutions of one step: ONE clear per step instead of one
-    hipMemsetAsync per launch (~70 per SGG_emb step).  ``reset()`` at the top of a step clears the prefix used
-    last step and rewinds; ``take()`` hands out channels_last tensors.  When it runs out it reports the size
-    it would have needed (``wanted``) and the conv falls back to clearing its own output."""
-
-    def __init__(self, nbytes, device):
-        self.buf = torch.zeros(max(int(nbytes), 1024) // 4, dtype=torch.float32, device=device)
-        self.off = self.used = self.wanted = 0
-
-    def reset(self):
-        # while a graph is being captured the clear must cover everything the captured step will take, whatever the
-        # eager steps before it used (an arena that was just re-sized has used == 0: a captured step without a clear
-        # node would accumulate into its own outputs of the previous replay)
-        n = self.buf.numel() if torch.cuda.is_current_stream_capturing() else self.used
-        if n:
-            self.buf[:n].zero_()
-        self.off = self.wanted = 0
-
-    def take(self, B, C, H, W):
-        n = B * C * H * W
-        n_al = (n + 63) // 64 * 64
-        self.wanted += n_al
-        if self.off + n_al > self.buf.numel():
-            return None
-        t = self.buf[self.off:self.off + n].view(B, H, W, C).permute(0, 3, 1, 2)
-        self.off += n_al
-        self.used = max(self.used, self.off)
-        return t
-
-    def take_flat(self, n):
-        """n zeros, contiguous (bias-gradient sums, small filter gradients that are accumulated atomically)."""
-        n_al = (n + 63) // 64 * 64
-        self.wanted += n_al
-        if self.off + n_al > self.buf.numel():
-            return None
-        t = self.buf[self.off:self.off + n]
-        self.off += n_al
-        self.used = max(self.used, self.off)
-        return t
-
-
 # Bumped whenever trained parameters change behind autograd's back (optim.FusedSGD writes through raw device pointers and
 # never touches ``Tensor._version``): part of the key of every cache derived from a trained parameter.
 PARAM_EPOCH = 0
@@ -404,192 +344,6 @@ def param_key(w):
 
 
 SMALL_GW_BYTES = 16 << 20
-ARENA = None        # set by a training step object (train.SGGEmbStep) around its forward/backward
-
-
-class SplitWorkspace:
-    """Caller-owned split-K scratch of the implicit-GEMM kernels (include/i2vsgg_hip.h, i2v_conv_fwd): arrival counters
-    (zero between launches) + a slab of partial tiles.  Launches that share one must be ordered on the device, so every
-    piece of work that may run CONCURRENTLY with another (two HIP graphs on two streams, two branches of one graph)
-    gets its own: a step object installs it in ``ops.SPLIT_WS`` around the code it captures.  Without one, calls use a
-    workspace per (device, launch stream)."""
-    BYTES = (48 << 20) + 4096
-
-    def __init__(self, device, nbytes=None):
-        self.buf = torch.zeros(int(nbytes or self.BYTES), dtype=torch.uint8, device=device)
-
-
-SPLIT_WS = None     # set like ARENA; None -> one workspace per launch stream
-_TUNE_SPLIT_ATOMICS = 4                 # include/i2vsgg_hip.h I2V_TUNE_SPLIT_ATOMICS
-ORDERED_SUMS = os.environ.get("I2V_ORDERED_SUMS", "1") != "0"     # 0: LaunchContext(ordered=True) is ignored (A/B of its cost)
-_split_ws_by_stream = {}
-
-
-class LaunchContext:
-    """What one independently scheduled piece of captured work owns exclusively: the pre-zeroed arena of its
-    atomically accumulated outputs, its split-K workspace and its tagged scratch buffers.  ``with ctx:`` installs them
-    for the calls made inside (forward AND the autograd backward triggered inside the block)."""
-
-    def __init__(self, device, arena=True, ordered=False):
-        self.device = torch.device(device)
-        self.arena = ZeroArena(1024, self.device) if arena else None      # sized after the first eager step (fit())
-        self.split = SplitWorkspace(self.device)
-        self.scratch = {}
-        # ordered: every reduction the launches of this context split across workgroups -- split-K GEMMs of any split count,
-        # small filter gradients, bias column sums -- is summed in a fixed order through ``split`` (I2V_TUNE_SPLIT_ATOMICS = 0
-        # while the context is entered): bit-reproducible results.  The relation step's head asks for it (free there); the
-        # instance_styleD step does not (+4 % of its step: DESIGN.md 5.10)
-        self.ordered = bool(ordered)
-
-    def fit(self):
-        """After an eager step: re-size the arena to what the step asked for."""
-        a = self.arena
-        if a is not None and a.wanted * 4 > a.buf.numel() * 4:
-            self.arena = ZeroArena(int(a.wanted * 4 * 1.05) + 4096, self.device)
-
-    def __enter__(self):
-        global ARENA, SPLIT_WS, SCRATCH
-        self._saved = (ARENA, SPLIT_WS, SCRATCH)
-        ARENA, SPLIT_WS, SCRATCH = self.arena, self.split, self.scratch
-        self._tune = None
-        if self.ordered and ORDERED_SUMS:
-            self._tune = lib.i2v_get_tuning(_TUNE_SPLIT_ATOMICS)
-            if self._tune == 2:             # an explicit I2V_SPLIT_ATOMICS=1 (always atomics) is the user's to keep
-                lib.i2v_set_tuning(_TUNE_SPLIT_ATOMICS, 0)
-        if self.arena is not None:
-            self.arena.reset()          # one clear for every atomically accumulated output of this piece of work
-        return self
-
-    def __exit__(self, *exc):
-        global ARENA, SPLIT_WS, SCRATCH
-        ARENA, SPLIT_WS, SCRATCH = self._saved
-        if self._tune == 2:
-            lib.i2v_set_tuning(_TUNE_SPLIT_ATOMICS, 2)
-        return False
-
-
-# ---------------------------------------------------------------------------------------------------------------------
-# Streams.  ``torch.cuda.Stream()`` does not create a stream: it deals the next of 32 pooled streams per device and priority,
-# round robin -- and torch.cuda.graph's capture stream, ProcessGroupNCCL's streams and every caller's own streams come out of the
-# same pool.  A process that has built a few step objects therefore holds "different" stream objects with the SAME handle, and
-# a fork onto an alias of the forking stream (or of a sibling branch) is no fork at all.  The step objects take their streams
-# from this registry instead: one HIP stream per (device, role), created ONCE per process by the library
-# (``i2v_stream_create``: hipStreamCreateWithPriority, non-blocking), wrapped as a ``torch.cuda.ExternalStream`` and never
-# destroyed.  Such a handle cannot come out of torch's pool, two roles never share one, and step objects built one after the
-# other reuse the same few streams (a stream is an ordered queue: sharing a role between objects that run one after the other
-# costs nothing).
-_ROLE_STREAMS = {}
-STREAM_REQUESTS = []    # every request in order (capped): with torch.cuda.Stream() each of them drew the next pooled handle
-
-
-def role_stream(device, role, priority=0):
-    """The process-wide stream of ``role`` (any hashable: "side", ("frame", 0), "copy", ...) on ``device``."""
-    dev = torch.device(device)
-    index = dev.index if dev.index is not None else torch.cuda.current_device()
-    key = (index, role, int(priority))
-    if len(STREAM_REQUESTS) < 4096:
-        STREAM_REQUESTS.append(role)
-    st = _ROLE_STREAMS.get(key)
-    if st is None:
-        import ctypes
-        torch.cuda.init()
-        out = ctypes.c_void_p()
-        check(lib.i2v_stream_create(index, int(priority), ctypes.byref(out)), "i2v_stream_create")
-        taken = {t.cuda_stream for t in _ROLE_STREAMS.values()}
-        if not out.value or out.value in taken:
-            raise _lib.I2VError("role_stream: the runtime handed out stream handle %r twice" % out.value)
-        st = _ROLE_STREAMS[key] = torch.cuda.ExternalStream(out.value, device=torch.device("cuda", index))
-    return st
-
-
-def stream_table():
-    """{(device, role, priority): handle} of every stream the registry has created (tools/stream_handles.py, tests)."""
-    return {k: v.cuda_stream for k, v in _ROLE_STREAMS.items()}
-
-
-_BRANCH_DEPTH = 0
-_FORKED = {}            # handle -> origin handle of every branch forked and not yet joined (ops.join)
-
-
-class branch:
-    """``with ops.branch(stream, origin):`` -- the body runs on ``stream`` as a fork of ``origin`` (stream.wait_stream(origin) first;
-    the caller joins with ``ops.join(origin, stream, ...)``).  The step objects fork their graph branches through this so that the
-    capture-time failures the schedule must avoid are error messages instead:
-      * a fork made INSIDE a forked branch ends ``hipStreamEndCapture`` in a host segfault on ROCm 7.2 -- every
-        branch forks from the capturing stream itself;
-      * a branch stream whose HANDLE equals the origin's, or that of a sibling branch still open, is not a branch (the work is
-        silently serialised, and events recorded "between" the two are edges of a stream onto itself)."""
-
-    def __init__(self, stream, origin):
-        self.stream, self.origin = stream, origin
-
-    def __enter__(self):
-        global _BRANCH_DEPTH
-        if _BRANCH_DEPTH > 0 and torch.cuda.is_current_stream_capturing():
-            raise RuntimeError("ops.branch: a fork inside a forked graph branch (hipStreamEndCapture crashes on it): fork every "
-                               "branch from the capturing stream")
-        h, ho = self.stream.cuda_stream, self.origin.cuda_stream
-        if h == ho:
-            raise RuntimeError("ops.branch: the branch stream IS the forking stream (handle %#x): take branch streams from "
-                               "ops.role_stream, torch.cuda.Stream() deals pooled handles round robin" % h)
-        if h in _FORKED:
-            raise RuntimeError("ops.branch: stream %#x is already an open branch (a sibling's alias?); join it first" % h)
-        self.stream.wait_stream(self.origin)
-        self._ctx = torch.cuda.stream(self.stream)
-        self._ctx.__enter__()
-        _FORKED[h] = ho
-        _BRANCH_DEPTH += 1
-        return self
-
-    def __exit__(self, *exc):
-        global _BRANCH_DEPTH
-        _BRANCH_DEPTH -= 1
-        if exc and exc[0] is not None:
-            _FORKED.pop(self.stream.cuda_stream, None)       # a failed body: whoever handles the error owns the clean-up
-        return self._ctx.__exit__(*exc)
-
-
-def reset_branches():
-    """After a failed capture: forget the branches it left open."""
-    global _BRANCH_DEPTH
-    _FORKED.clear()
-    _BRANCH_DEPTH = 0
-
-
-def join(origin, *streams):
-    """``origin`` waits for every branch in ``streams`` (the join of ``ops.branch``)."""
-    for st in streams:
-        origin.wait_stream(st)
-        _FORKED.pop(st.cuda_stream, None)
-
-
-def _sws_args(device=None):
-    """(pointer, bytes) of the split workspace in force: what the ordered cross-workgroup sums of round 5 (bias column sums,
-    split filter gradients) need next to the split-K GEMMs."""
-    t = _split_ws(device if device is not None else torch.device("cuda", torch.cuda.current_device()))
-    return ptr(t), t.numel()
-
-
-def _split_ws(device):
-    ws = SPLIT_WS
-    if ws is None:
-        key = (device.index if device.index is not None else torch.cuda.current_device(), stream())
-        ws = _split_ws_by_stream.get(key)
-        if ws is None:
-            ws = _split_ws_by_stream[key] = SplitWorkspace(device)
-    return ws.buf
-
-
-_side_ws = {}
-
-
-def _side_split_ws(device):
-    """The split workspace of the filter-gradient side branch (one per device: the branch is one ordered stream)."""
-    key = device.index if device.index is not None else torch.cuda.current_device()
-    ws = _side_ws.get(key)
-    if ws is None:
-        ws = _side_ws[key] = SplitWorkspace(device)
-    return ws.buf
 
 
 def _conv_fwd_raw(x, w, scale, shift, res, stride, pad, flags, out=None):
@@ -598,7 +352,7 @@ def _conv_fwd_raw(x, w, scale, shift, res, stride, pad, flags, out=None):
     Ho = (H + 2 * pad - KH) // stride + 1
     Wo = (W + 2 * pad - KW) // stride + 1
     y = None
-    sws = _split_ws(x.device)
+    sws = launch.split_buffer(x.device)
     atomics = lib.i2v_conv_fwd_splits(B, H, W, Cin, Cout, KH, KW, stride, pad, sws.numel()) == 1
     if out is not None and not atomics:
         # the caller's buffer (a step's static feature-map buffer: no copy afterwards); only when the launch does not
@@ -606,8 +360,9 @@ def _conv_fwd_raw(x, w, scale, shift, res, stride, pad, flags, out=None):
         if tuple(out.shape) != (B, Cout, Ho, Wo) or not out.is_contiguous(memory_format=_CL) or out.dtype != torch.float32:
             raise ValueError("conv2d(out=...): needs a (%d,%d,%d,%d) channels_last fp32 tensor" % (B, Cout, Ho, Wo))
         y = out
-    if y is None and ARENA is not None and atomics:
-        y = ARENA.take(B, Cout, Ho, Wo)
+    arena = launch.arena()
+    if y is None and arena is not None and atomics:
+        y = arena.take(B, Cout, Ho, Wo)
         if y is not None:
             flags |= EPI_ZEROED
     if y is None:
@@ -658,8 +413,8 @@ def _conv_dgrad_raw(g, w, in_shape, stride, pad):
         w = torch.cat([w, w.new_zeros((padc,) + tuple(w.shape[1:]))], 0).contiguous(memory_format=_CL)
         Cout += padc
     gx = torch.empty((B, Cin, H, W), device=dev, dtype=torch.float32, memory_format=_CL)
-    ws = workspace(lib.i2v_conv_dgrad_workspace_bytes(Cin, Cout, KH, KW), dev, "dgrad")
-    sws = _split_ws(dev)
+    ws = launch.workspace(lib.i2v_conv_dgrad_workspace_bytes(Cin, Cout, KH, KW), dev, "dgrad")
+    sws = launch.split_buffer(dev)
     with _Timed(2.0 * B * g.shape[2] * g.shape[3] * Cout * KH * KW * Cin, "dgrad",
                 "M%d N%d K%d" % (B * H * W, Cin, KH * KW * Cout), 4 * (g.numel() + w.numel() + gx.numel())):
         check(lib.i2v_conv_dgrad(ptr(g), ptr(w), ptr(gx), B, H, W, Cin, Cout, KH, KW, stride, pad, ptr(ws), ws.numel(),
@@ -687,16 +442,16 @@ def _conv_wgrad_raw(x, g, w_shape, stride, pad, tag="wgrad", row_scale=None, win
     n = Cout * Cin * KH * KW
     # up to 224 pixels the launcher never splits the reduction (fewer than 8 stages of 32): one workgroup per tile
     # stores its result directly -- no zeroed output, no atomics
-    if ARENA is not None and n * 4 <= SMALL_GW_BYTES and B * g.shape[2] * g.shape[3] > 224:
-        flat = ARENA.take_flat(n)
+    arena = launch.arena()
+    if arena is not None and n * 4 <= SMALL_GW_BYTES and B * g.shape[2] * g.shape[3] > 224:
+        flat = arena.take_flat(n)
         if flat is not None:
             gw, beta = flat.view(Cout, KH, KW, Cin).permute(0, 3, 1, 2), 1.0
     if gw is None:
         gw = torch.empty(w_shape, device=x.device, dtype=torch.float32, memory_format=_CL)
     if winograd and _winograd_wgrad_ok(x, w_shape, stride, pad):
         # stride-1 / pad-1 3x3 layer of a trained bottleneck: 36 plane GEMMs over the 4x4 tiles, a quarter of the MACs
-        # a scratch buffer of its own: filter gradients may run on a side branch beside the Winograd data gradients
-        ws = workspace(lib.i2v_conv3x3_winograd4_wgrad_workspace_bytes(B, H, W, Cin, Cout), x.device, "winograd_wgrad")
+        ws = launch.workspace(lib.i2v_conv3x3_winograd4_wgrad_workspace_bytes(B, H, W, Cin, Cout), x.device, "winograd_wgrad")
         T = B * ((H + 3) // 4) * ((W + 3) // 4)
         with _Timed(2.0 * B * H * W * Cout * 9 * Cin, tag, "N%d K%d M%d (3x3 winograd F4)" % (Cout, 9 * Cin, B * H * W),
                     4 * (x.numel() + g.numel() + gw.numel())):
@@ -710,12 +465,9 @@ def _conv_wgrad_raw(x, g, w_shape, stride, pad, tag="wgrad", row_scale=None, win
     with _Timed(2.0 * B * g.shape[2] * g.shape[3] * Cout * KH * KW * Cin, tag,
                 "N%d K%d M%d" % (Cout, KH * KW * Cin, B * g.shape[2] * g.shape[3]) + (" (wgrad form)" if tag != "wgrad" else ""),
                 4 * (x.numel() + g.numel() + gw.numel())):
-        # ordered sum of a split reduction (bit-reproducible; no atomics, no clear) through the split workspace in force.  A call
-        # on the filter-gradient side branch (InstanceStyleDStep.wgrad_branch) runs beside the main chain's GEMMs that own that
-        # workspace -- launches sharing one must be ordered on the device -- so the side branch has a workspace of its own
-        # (round 6; round 5 left its sums on atomics)
-        side = WGRAD_STREAM is not None and torch.cuda.current_stream().cuda_stream == WGRAD_STREAM.cuda_stream
-        sws = _side_split_ws(x.device) if side else _split_ws(x.device)
+        # ordered sum of a split reduction (bit-reproducible; no atomics, no clear) through the current context's split
+        # workspace (on the filter-gradient side branch: the side context's own, launch.SideBranch)
+        sws = launch.split_buffer(x.device)
         if row_scale is not None:
             check(lib.i2v_conv_wgrad_scaled(ptr(x), ptr(g), ptr(row_scale), ptr(gw), B, H, W, Cin, Cout, KH, KW, stride, pad,
                                             beta, ptr(sws), sws.numel(), stream()), "conv_wgrad_scaled")
@@ -809,7 +561,8 @@ class _ConvFn(torch.autograd.Function):
         need_res = has_res and ctx.needs_input_grad[4]
         gbias = None
         if need_bias:
-            gbias = ARENA.take_flat(N) if ARENA is not None else None
+            arena = launch.arena()
+            gbias = arena.take_flat(N) if arena is not None else None
             if gbias is None:
                 gbias = torch.zeros((N,), device=gy.device, dtype=torch.float32)
 
@@ -825,7 +578,7 @@ class _ConvFn(torch.autograd.Function):
             if ctx.needs_input_grad[0] and not ctx.wino_dgrad and _linear_dgrad_as_wgrad(x.shape, w.shape, stride, pad):
                 g_t = torch.empty((N, M, 1, 1), device=gy.device, dtype=torch.float32)
             check(lib.i2v_epilogue_bwd(ptr(gy), ptr(y), ptr(scale) if has_scale else None, ptr(g), ptr(gpre), ptr(gbias),
-                                       M, N, int(relu), ptr(g_t), *_sws_args(), stream()), "epilogue_bwd")
+                                       M, N, int(relu), ptr(g_t), *launch.split_args(), stream()), "epilogue_bwd")
             if g is None:
                 g = gy
             if need_res:
@@ -864,8 +617,8 @@ def _dgrad_fused(g, w, in_shape, pad, gy_scale=None, out_scale=None, res=None, m
     B, Cin, H, W = in_shape
     Cout, _, KH, KW = w.shape
     gx = torch.empty((B, Cin, H, W), device=g.device, dtype=torch.float32, memory_format=_CL)
-    ws = workspace(lib.i2v_conv_dgrad_workspace_bytes(Cin, Cout, KH, KW), g.device, "dgrad")
-    sws = _split_ws(g.device)
+    ws = launch.workspace(lib.i2v_conv_dgrad_workspace_bytes(Cin, Cout, KH, KW), g.device, "dgrad")
+    sws = launch.split_buffer(g.device)
     extra = (res.numel() if res is not None else 0) + (mask.numel() if mask is not None else 0)
     with _Timed(2.0 * B * g.shape[2] * g.shape[3] * Cout * KH * KW * Cin, "dgrad", "M%d N%d K%d +epi" % (B * H * W, Cin, KH * KW * Cout),
                 4 * (g.numel() + w.numel() + gx.numel() + extra)):
@@ -885,7 +638,7 @@ def _winograd_dgrad_fused(g, U, out_scale, mask):
     B, Cout, H, W = g.shape
     Cin = U.shape[1]
     gx = torch.empty((B, Cin, H, W), device=g.device, dtype=torch.float32, memory_format=_CL)
-    ws = workspace(lib.i2v_conv3x3_winograd4_workspace_bytes(B, H, W, Cout, Cin), g.device, "winograd")
+    ws = launch.workspace(lib.i2v_conv3x3_winograd4_workspace_bytes(B, H, W, Cout, Cin), g.device, "winograd")
     T = B * ((H + 3) // 4) * ((W + 3) // 4)
     with _Timed(2.0 * B * H * W * Cout * 9 * Cin, "dgrad",
                 "M%d N%d K%d (3x3 winograd F4) gemmMB=%.2f +epi" % (B * H * W, Cin, 9 * Cout, 4e-6 * 36 * (T * Cout + Cout * Cin + T * Cin)),
@@ -893,25 +646,6 @@ def _winograd_dgrad_fused(g, U, out_scale, mask):
         check(lib.i2v_conv3x3_winograd4_dgrad(ptr(g), ptr(U), ptr(out_scale), ptr(mask), ptr(gx), B, H, W, Cout, Cin, ptr(ws),
                                               ws.numel(), stream()), "conv3x3_winograd4_dgrad")
     return gx
-
-
-# Filter gradients of the block nodes on a side branch of the captured step (train.InstanceStyleDStep sets the stream): they
-# depend on the data-gradient chain but nothing in the backward depends on them, so they can fill the chip beside it.  One
-# edge per block (the side branch waits for the block's data gradients), one join before the gradient exchange.  The tensors
-# a side launch reads are kept referenced until the join (WGRAD_PENDING): in a captured step a block freed on the main
-# branch would otherwise be handed to a later main-branch allocation while the side branch still reads it.
-WGRAD_STREAM = None
-WGRAD_PENDING = []
-
-
-def join_wgrad_branch():
-    """Called by the step after backward(): the capturing stream waits for the filter-gradient branch."""
-    if WGRAD_STREAM is not None:
-        cur = torch.cuda.current_stream()
-        if WGRAD_STREAM.cuda_stream == cur.cuda_stream:
-            raise RuntimeError("join_wgrad_branch: the filter-gradient stream is the current stream")
-        cur.wait_stream(WGRAD_STREAM)
-    WGRAD_PENDING.clear()
 
 
 class _BottleneckFn(torch.autograd.Function):
@@ -966,7 +700,7 @@ class _BottleneckFn(torch.autograd.Function):
         else:       # the consumers of ``out`` know nothing of its ReLU: one masking pass
             gpre = torch.empty_like(g)
             M, N = g.shape[0] * g.shape[2] * g.shape[3], g.shape[1]
-            check(lib.i2v_epilogue_bwd(ptr(g), ptr(out), None, ptr(gpre), None, None, M, N, 1, None, *_sws_args(), stream()), "epilogue_bwd")
+            check(lib.i2v_epilogue_bwd(ptr(g), ptr(out), None, ptr(gpre), None, None, M, N, 1, None, *launch.split_args(), stream()), "epilogue_bwd")
         st = ctx.stride
         # ---- data gradients (the chain the rest of the backward waits for)
         g2 = _dgrad_fused(gpre, w3, a2.shape, 0, gy_scale=s3, out_scale=s2, mask=a2)         # gradient at conv2's raw output
@@ -988,14 +722,8 @@ class _BottleneckFn(torch.autograd.Function):
             gw1 = _conv_wgrad_raw(x, g1, w1.shape, st, 0) if need[1] else None
             gwd = _conv_wgrad_raw(x, gpre, wd.shape, st, 0, row_scale=sd) if (has_ds and need[4]) else None
             return gw1, gw2, gw3, gwd
-        side = WGRAD_STREAM
-        if side is not None:
-            side.wait_stream(torch.cuda.current_stream())
-            WGRAD_PENDING.append((x, a1, a2, v2, gpre, g2, g1))
-            with torch.cuda.stream(side):
-                gw1, gw2, gw3, gwd = wgrads()
-        else:
-            gw1, gw2, gw3, gwd = wgrads()
+        side = launch.WGRAD_BRANCH
+        gw1, gw2, gw3, gwd = side.run(wgrads, x, a1, a2, v2, gpre, g2, g1) if side is not None else wgrads()
         return (gx, gw1, gw2, gw3, gwd) + (None,) * 12
 
 
@@ -1162,7 +890,7 @@ class _DStyleFusedFn(torch.autograd.Function):
         z = torch.empty((n_img, dim), device=dev, dtype=torch.float32)
         x1 = torch.empty((M, N), device=dev, dtype=torch.float32) if keep else None
         x2 = torch.empty((M, N), device=dev, dtype=torch.float32) if keep else None
-        ws = workspace(lib.i2v_dstyle_fused_workspace_bytes(P, n_img, dim, rank), dev, "dstyle")
+        ws = launch.workspace(lib.i2v_dstyle_fused_workspace_bytes(P, n_img, dim, rank), dev, "dstyle")
         with _Timed(2.0 * 2 * M * N * K, "fwd", "dstyle fused M%d N2x%d K%d" % (M, N, K),
                     4 * (rows.numel() + 2 * w1.numel() + (2 * M * N if keep else 0))):
             check(lib.i2v_dstyle_fused_fwd(ptr(rows), ptr(w1), ptr(b1.contiguous()), ptr(w2), ptr(b2.contiguous()), ptr(z),
@@ -1189,10 +917,11 @@ class _DStyleFusedFn(torch.autograd.Function):
             g4 = g.view(M, N, 1, 1)
             gb = None
             if need_b:
-                gb = ARENA.take_flat(N) if ARENA is not None else None
+                arena = launch.arena()
+                gb = arena.take_flat(N) if arena is not None else None
                 if gb is None:
                     gb = torch.zeros((N,), device=g.device, dtype=torch.float32)
-                check(lib.i2v_epilogue_bwd(ptr(g), None, None, None, None, ptr(gb), M, N, 0, None, *_sws_args(), stream()), "epilogue_bwd")
+                check(lib.i2v_epilogue_bwd(ptr(g), None, None, None, None, ptr(gb), M, N, 0, None, *launch.split_args(), stream()), "epilogue_bwd")
             gw = _conv_wgrad_raw(rows4, g4, (N, K, 1, 1), 1, 0).view(N, K) if need_w else None
             gx = _conv_dgrad_raw(g4, w.view(N, K, 1, 1), (M, K, 1, 1), 1, 0).view(M, K) if ctx.needs_input_grad[0] else None
             outs.append((gx, gw, gb))
@@ -1241,7 +970,7 @@ class _DPixelFn(torch.autograd.Function):
         gh2 = torch.empty((M, 128), device=dev, dtype=torch.float32)
         gh1 = torch.empty((M, 512), device=dev, dtype=torch.float32)
         gx = torch.empty((M, 1024), device=dev, dtype=torch.float32)
-        ws = workspace(lib.i2v_dpixel_bwd_workspace_bytes(), dev, "dpixel")
+        ws = launch.workspace(lib.i2v_dpixel_bwd_workspace_bytes(), dev, "dpixel")
         check(lib.i2v_dpixel_bwd(ptr(gd), ptr(gfeat), ptr(d), ptr(h1), ptr(h2), ptr(w1), ptr(w2), ptr(w3), ptr(g3), ptr(gh2),
                                  ptr(gh1), ptr(gx), M, pix, lamb, ptr(ws), ws.numel(), stream()), "dpixel_bwd")
         as4 = lambda t: t.view(M, -1, 1, 1)
@@ -1286,7 +1015,7 @@ def detection_postprocess(rois, cls_prob, bbox_pred, im_h, im_w, im_scale, class
     else:
         dets = torch.empty((C, R, 5), device=dev, dtype=torch.float32)
         counts = torch.empty((C,), device=dev, dtype=torch.int32)
-    ws = workspace(lib.i2v_det_postprocess_workspace_bytes(R, C), dev, "det")
+    ws = launch.workspace(lib.i2v_det_postprocess_workspace_bytes(R, C), dev, "det")
     f4 = lambda v: (ctypes.c_float * 4)(*[float(t) for t in v]) if v is not None else None
     if im_info is not None:
         _need_cuda(im_info)
@@ -1338,7 +1067,7 @@ def relation_topk(rel_score, conf, ixs, ixo, k=100):
     pair = torch.empty((k,), device=dev, dtype=torch.int32)
     pred = torch.empty((k,), device=dev, dtype=torch.int32)
     out = torch.empty((k,), device=dev, dtype=torch.float32)
-    ws = workspace(lib.i2v_relation_topk_workspace_bytes(n_pairs, n_rel), dev, "reltopk")
+    ws = launch.workspace(lib.i2v_relation_topk_workspace_bytes(n_pairs, n_rel), dev, "reltopk")
     check(lib.i2v_relation_topk(ptr(rel_score), ptr(conf), ptr(ixs), ptr(ixo), n_pairs, n_rel, k, ptr(pair), ptr(pred), ptr(out),
                                 ptr(ws), ws.numel(), stream()), "relation_topk")
     return pair, pred, out
@@ -1373,7 +1102,7 @@ def video_associate(frame_off, frame_no, pred_off, score, triplet, boxes, device
     rel_score = torch.zeros((P,), device=dev, dtype=torch.float64)
     n_rel = torch.zeros((max(V, 0),), device=dev, dtype=torch.int32)
     with torch.cuda.device(dev):
-        ws = workspace(lib.i2v_video_associate_workspace_bytes(V, F, P), dev, "video")
+        ws = launch.workspace(lib.i2v_video_associate_workspace_bytes(V, F, P), dev, "video")
         check(lib.i2v_video_associate(ptr(frame_off), ptr(frame_no), ptr(pred_off), ptr(score), ptr(triplet), ptr(boxes), V, F, P,
                                       max_per_frame, ptr(rel_id), ptr(rel_start), ptr(rel_len), ptr(rel_score), ptr(n_rel),
                                       ptr(ws), ws.numel(), stream()), "video_associate")
@@ -1401,7 +1130,7 @@ def video_viou_match(pred_off, pred_rel, pred_score, gt_off, gt_rel, boxes, viou
     hit = torch.full((NP,), -1, device=dev, dtype=torch.int32)
     hit_ov = torch.full((NP,), -1.0, device=dev, dtype=torch.float64)
     with torch.cuda.device(dev):
-        ws = workspace(lib.i2v_video_viou_match_workspace_bytes(NP, NG), dev, "video")
+        ws = launch.workspace(lib.i2v_video_viou_match_workspace_bytes(NP, NG), dev, "video")
         check(lib.i2v_video_viou_match(ptr(pred_off), ptr(pred_rel), ptr(pred_score), ptr(gt_off), ptr(gt_rel), ptr(boxes), V, NP,
                                        NG, NB, max_pred, max_gt, float(viou_threshold), ptr(ov), ptr(hit), ptr(hit_ov),
                                        ptr(ws), ws.numel(), stream()), "video_viou_match")
@@ -1436,7 +1165,7 @@ def det_eval_match(seg_det_off, seg_gt, gt_off, det_key, det_box, gt_box, gt_har
     ovmax = torch.full((D,), float("-inf"), device=dev, dtype=torch.float64)
     jmax = torch.full((D,), -1, device=dev, dtype=torch.int32)
     with torch.cuda.device(dev):
-        ws = workspace(lib.i2v_det_eval_match_workspace_bytes(D), dev, "det_eval")
+        ws = launch.workspace(lib.i2v_det_eval_match_workspace_bytes(D), dev, "det_eval")
         check(lib.i2v_det_eval_match(ptr(seg_det_off), ptr(seg_gt), ptr(gt_off), ptr(det_key), ptr(det_box), ptr(gt_box),
                                      ptr(gt_hard), S, D, NS, G, max_gt, float(ovthresh), ptr(flag), ptr(ovmax), ptr(jmax),
                                      ptr(ws), ws.numel(), stream()), "det_eval_match")
@@ -1458,7 +1187,7 @@ def det_eval_curve(det_key, cls_off, flag, npos, device=None):
     rec, prec = (torch.zeros((D,), device=dev, dtype=torch.float64) for _ in range(2))
     ap_area, ap_11pt = (torch.zeros((C,), device=dev, dtype=torch.float64) for _ in range(2))
     with torch.cuda.device(dev):
-        ws = workspace(lib.i2v_det_eval_curve_workspace_bytes(D), dev, "det_eval")
+        ws = launch.workspace(lib.i2v_det_eval_curve_workspace_bytes(D), dev, "det_eval")
         check(lib.i2v_det_eval_curve(ptr(det_key), ptr(cls_off), ptr(flag), ptr(npos), C, D, ptr(perm), ptr(cum_tp), ptr(cum_fp),
                                      ptr(rec), ptr(prec), ptr(ap_area), ptr(ap_11pt), ptr(ws), ws.numel(), stream()),
               "det_eval_curve")
@@ -1693,7 +1422,7 @@ def conv3x3_winograd(x, U, scale=None, shift=None, relu=False, tag="fwd", keep_v
     y = torch.empty((B, Cout, H, W), device=x.device, dtype=torch.float32, memory_format=_CL)
     four = U.shape[0] == 36          # F(4x4,3x3)
     wsb = (lib.i2v_conv3x3_winograd4_workspace_bytes if four else lib.i2v_conv3x3_winograd_workspace_bytes)(B, H, W, Cin, Cout)
-    ws = workspace(wsb, x.device, "winograd")
+    ws = launch.workspace(wsb, x.device, "winograd")
     fn = lib.i2v_conv3x3_winograd4_fwd if four else lib.i2v_conv3x3_winograd_fwd
     # the batched GEMM of the call is one conv_gemm_f32 launch over the planes: its operand bytes, for the traffic roofline
     planes, tl = (36, 4) if four else (16, 2)

@@ -3,7 +3,7 @@ slots that cross PCIe as one copy, and the copy-stream uploader."""
 import numpy as np
 import torch
 
-from . import ops
+from . import launch, ops
 from . import synthetic as syn
 from .model.utils.config import cfg
 
@@ -106,7 +106,7 @@ class _Slot:
 
 
 class _Uploader:
-    """Host frames -> device on the process's COPY stream (ops.role_stream), two staging buffers and event edges both ways: the
+    """Host frames -> device on the process's COPY stream (launch.role_stream), two staging buffers and event edges both ways: the
     transfer of minibatch k+1 runs beside the step that is still computing (a 2 x 3 x 600 x 1000 fp32 minibatch is 14.4 MB;
     bench.py --data loader over four alternating frame sizes: 5.00 -> 4.82 ms per step, uint8 frames 4.83 -> 4.77).
     ``I2V_UPLOAD_STREAM=0``: the transfer on the caller's stream, in front of the step (the default of round 3, which had met
@@ -115,7 +115,7 @@ class _Uploader:
     neither crashes (profiles/r04_alias_repro.txt; that record stopped on a bookkeeping KeyError of the test before the numeric
     comparison) nor changes a loss or a weight (profiles/r05_alias_repro.txt: run to the end, 18 passed) once no graph is
     dropped while a replay of it may be in flight (``invalidate_graphs`` synchronises first; stage() grew the head capacity
-    and dropped every graph right behind an asynchronous replay).  The aliases cost the overlap, not correctness; they are gone too (ops.role_stream),
+    and dropped every graph right behind an asynchronous replay).  The aliases cost the overlap, not correctness; they are gone too (launch.role_stream),
     and tests/test_gpu_data_layer.py runs the loader loop both ways, in the order that crashed.
     ``upload`` returns a device tensor that is valid on the caller's CURRENT stream, ``consumed`` marks the point after which
     its buffer may be overwritten."""
@@ -129,9 +129,9 @@ class _Uploader:
         # alternates between the graphs of two sizes -- so it is not the default.
         import os
         self.enabled = os.environ.get("I2V_UPLOAD_STREAM", "1") == "1"
-        # the copy stream exists only when asked for, and is the process's ONE copy stream (ops.role_stream): a handle of the
+        # the copy stream exists only when asked for, and is the process's ONE copy stream (launch.role_stream): a handle of the
         # library's own, never an alias of a branch / capture / communicator stream out of torch's pool
-        self.stream = ops.role_stream(self.dev, "copy", 0) if self.enabled else None      # normal priority: a high one doubles the step when the loop alternates between the graphs of two sizes
+        self.stream = launch.role_stream(self.dev, "copy", 0) if self.enabled else None      # normal priority: a high one doubles the step when the loop alternates between the graphs of two sizes
         self.rings = {}
 
     def upload(self, frames):

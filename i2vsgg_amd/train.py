@@ -13,7 +13,7 @@ and ``replay_graph`` are imported here under the names callers have always used 
 import numpy as np
 import torch
 
-from . import _lib, ops, parallel
+from . import _lib, launch, ops, parallel
 from . import synthetic as syn
 from .graphs import CapturedStep, replay_graph, _REPLAY_STREAMS                                   # noqa: F401
 from .model.utils.config import cfg
@@ -29,7 +29,7 @@ class _FrameSet:
         n, h, w = key
         self.key = key
         self.im = torch.zeros((n, 4, h, w), device=device).contiguous(memory_format=torch.channels_last)
-        self.ctx = [ops.LaunchContext(device, arena=arena) for _ in range(n_ctx)]
+        self.ctx = [launch.LaunchContext(device, arena=arena) for _ in range(n_ctx)]
         self.fh = self.fw = None      # extent of the C4 map, known after the first pass
         self.graph = None             # None: not captured yet; False: capture failed (eager launches for this size)
         self.fitted = False
@@ -37,8 +37,8 @@ class _FrameSet:
         # stage-split schedule (round 6): this size as the FRONT half's (stem .. layer3[:cut]) and as the BACK half's
         # (layer3[cut:]) input; a graph is captured per (front size, back size) pair -- the back half of a call works on the
         # previous minibatch, whose size may differ
-        self.ctx_front = ops.LaunchContext(device, arena=arena)
-        self.ctx_back = ops.LaunchContext(device, arena=arena)
+        self.ctx_front = launch.LaunchContext(device, arena=arena)
+        self.ctx_back = launch.LaunchContext(device, arena=arena)
         self.fitted_front = self.fitted_back = False
         self.graphs = {}              # back size key -> graph (or False)
 
@@ -88,7 +88,7 @@ class SGGEmbStep(CapturedStep):
     Schedule (``overlap``, the default with HIP graphs): the backbone is frozen in this loop, so the backbone pass of
     the NEXT minibatch does not depend on this step's update.  The whole step is ONE captured graph with branches
     between a fork and a join: [head fwd + bwd (+ exchange) + SGD of batch k] beside [backbone of batch k+1, one branch per
-    frame].  The branches own disjoint device state (``ops.LaunchContext``: zero arena, split-K workspace, scratch) and
+    frame].  The branches own disjoint device state (``launch.LaunchContext``: zero arena, split-K workspace, scratch) and
     meet only at graph edges: the feature-map hand-off (one copy before the fork) and the join.  There is one graph launch
     per step on the caller's stream, no side stream, no event and no priority for a caller to get wrong.
 
@@ -160,7 +160,7 @@ class SGGEmbStep(CapturedStep):
         # than a third of the stage (ResNet-50 has 6)
         n3 = len(net.RCNN_base[6])
         self.cut = max(1, min(int(os.environ.get("I2V_STAGE_CUT", "6")), max(n3 // 3, 1), n3 - 1))
-        self._frame_streams = [ops.role_stream(self.dev, ("frame", f)) for f in range(max(n_frames, 2))] \
+        self._frame_streams = [launch.role_stream(self.dev, ("frame", f)) for f in range(max(n_frames, 2))] \
             if (self.bb_split or self.stage_split) else []
         # host-side twins of the three head-input slots (which minibatch each holds) and of what the head has trained: with
         # the backbone cut by stage a batch reaches the head two calls after its stage(); in a loop that stages a new batch
@@ -170,8 +170,8 @@ class SGGEmbStep(CapturedStep):
         self.mid_next_flat = self.mid_cur_flat = None
         self.mid_slot = None
         self._side = None
-        self.ctx_head = ops.LaunchContext(self.dev, arena=zero_arena, ordered=True)      # head branch: bit-reproducible sums
-        self.ctx_bb = ops.LaunchContext(self.dev, arena=zero_arena)        # eager backbone passes (any size)
+        self.ctx_head = launch.LaunchContext(self.dev, arena=zero_arena, ordered=True)      # head branch: bit-reproducible sums
+        self.ctx_bb = launch.LaunchContext(self.dev, arena=zero_arena)        # eager backbone passes (any size)
         self.shapes, self.max_graphs, self._tick, self._pool = {}, int(max_graphs), 0, None
         self.cap_boxes, self.cap_pairs = n_frames * n_boxes, n_frames * n_pairs      # rows of the padded head inputs
         self.cap_cells = 0
@@ -492,12 +492,12 @@ class SGGEmbStep(CapturedStep):
         n = fs.key[0]
         for f in range(n):
             st = self._frame_streams[f]
-            with ops.branch(st, main):
+            with launch.branch(st, main):
                 with fs.ctx[f]:
                     with torch.no_grad():
                         self.net.RCNN_base(fs.im[f:f + 1], out=self._fmap_dst(fs, f))
         if join:
-            ops.join(main, *self._frame_streams[:n])
+            launch.join(main, *self._frame_streams[:n])
         self._fmap_key = fs.key
 
     TRACE_COLS = ("loss", "features", "scores", "embedding", "rng_canary", "fc7_weight", "fc6_weight_head", "boxes", "labels")
@@ -558,22 +558,22 @@ class SGGEmbStep(CapturedStep):
             fb = self.shapes[self._mid_key]         # the minibatch whose front half ran in the previous call
             self.mid_cur_flat.copy_(self.mid_next_flat)
             sa, sb = self._frame_streams[0], self._frame_streams[1]
-            with ops.branch(sa, main):
+            with launch.branch(sa, main):
                 self._front(fs, fs.ctx_front)
-            with ops.branch(sb, main):
+            with launch.branch(sb, main):
                 self._back(fb, fb.ctx_back)
             self._head()
-            ops.join(main, sa, sb)
+            launch.join(main, sa, sb)
             return
         if self.bb_split:                   # one branch per frame, forked from the capturing stream itself (a fork inside a
             self._backbone_per_frame(fs, join=False)      # forked branch crashes hipStreamEndCapture on ROCm 7.2)
             self._head()
-            ops.join(main, *self._frame_streams[:fs.key[0]])
+            launch.join(main, *self._frame_streams[:fs.key[0]])
             return
-        with ops.branch(self._side, main):
+        with launch.branch(self._side, main):
             self._backbone(fs)              # batch k+1
         self._head()                        # batch k
-        ops.join(main, self._side)
+        launch.join(main, self._side)
 
     def prime(self):
         """Overlapped schedule only: backbone pass of the batch staged first, so that the first call's head finds its
@@ -688,7 +688,7 @@ class SGGEmbStep(CapturedStep):
         else:
             self._evict_lru([(f, None) for f in self.shapes.values() if f.graph])
         if self._pipelined and self._side is None:
-            self._side = ops.role_stream(self.dev, "side")
+            self._side = launch.role_stream(self.dev, "side")
         fmap_key = self._fmap_key
         try:                          # (the recording starts with a device synchronisation: the fitting passes above are finished)
             g = self._record_graph((lambda: self._body_overlapped(fs)) if self._pipelined else self._body)      # fs is the staged set
@@ -799,9 +799,9 @@ class _DomainSet:
         self.im_st = z(2 * n, hs, ws) if (batched and (hs, ws) == (ht, wt)) else None
         # ordered=True (round 6): every split reduction of the detector step in a fixed order -- bit-reproducible steps at
         # +0.3 % (round 5: +4 %, most of it ONE unsplit 18-row filter gradient)
-        self.ctx = ops.LaunchContext(device, ordered=True)
-        self.ctx_src = ops.LaunchContext(device, ordered=True) if branches else None
-        self.ctx_tgt = ops.LaunchContext(device, ordered=True) if branches else None
+        self.ctx = launch.LaunchContext(device, ordered=True)
+        self.ctx_src = launch.LaunchContext(device, ordered=True) if branches else None
+        self.ctx_tgt = launch.LaunchContext(device, ordered=True) if branches else None
         self.graph = None             # None: not captured yet; False: capture failed (eager launches for this key)
         self.fitted = False
         self.tick = 0
@@ -837,14 +837,14 @@ class InstanceStyleDStep(CapturedStep):
         self.n_frames, self.n_gt = n_frames, n_gt
         import os
         self.batched = True
-        # filter gradients of the bottleneck nodes on a side branch of the step (ops.WGRAD_STREAM)
+        # filter gradients of the bottleneck nodes on a side branch of the step (launch.SideBranch)
         # (only with the one-pass backbone: a filter met twice in one backward would have its two gradients added on the main
         # stream while the side branch may still be writing the first)
         self.wgrad_branch = False      # filter gradients on a side branch: -1 % of the step for +2.4 GB; a test sets it
-        self._wgrad_stream = ops.role_stream(self.dev, "wgrad") if self.wgrad_branch else None
+        self._wgrad_stream = launch.role_stream(self.dev, "wgrad") if self.wgrad_branch else None
         # the captured step: source and target as two branches of the graph (_body_branches)
         self.branches = os.environ.get("I2V_ISD_BRANCHES", "1") != "0" and self.dev.type == "cuda" and not self.wgrad_branch
-        self._branch_streams = [ops.role_stream(self.dev, ("domain", i)) for i in range(2)] if self.branches else []
+        self._branch_streams = [launch.role_stream(self.dev, ("domain", i)) for i in range(2)] if self.branches else []
         self.sets, self.max_graphs, self._tick, self._pool = {}, int(max_graphs), 0, None
         self._cur = None              # the _DomainSet staged last
         self._uploader = None
@@ -998,12 +998,13 @@ class InstanceStyleDStep(CapturedStep):
                 vals.update(cst)
             vals["total"] = total
             self.opt.zero_grad()
-            ops.WGRAD_STREAM = self._wgrad_stream if self.wgrad_branch else None
+            side = launch.WGRAD_BRANCH = launch.SideBranch(self._wgrad_stream) if self.wgrad_branch else None
             try:
                 (total / self.world).backward()
-                ops.join_wgrad_branch()
+                if side is not None:
+                    side.join()
             finally:
-                ops.WGRAD_STREAM = None
+                launch.WGRAD_BRANCH = None
             parallel.all_reduce_grads(self.opt.params())
             self.opt.step()
             self._loss_buf.copy_(torch.stack([vals[k].detach().reshape(()) for k in self.names]))
@@ -1056,11 +1057,11 @@ class InstanceStyleDStep(CapturedStep):
         exchange = parallel.exchange_enabled()
         marks = {}
         try:
-            with ops.branch(s_src, main), self.ctx_src:
+            with launch.branch(s_src, main), self.ctx_src:
                 self._marks = marks["s"] = parallel.BucketMarks(True) if exchange else None
                 v, grads["s"] = source()
                 vals.update(v)
-            with ops.branch(s_tgt, main), self.ctx_tgt:
+            with launch.branch(s_tgt, main), self.ctx_tgt:
                 self._marks = marks["t"] = parallel.BucketMarks(True) if exchange else None
                 v, grads["t"] = target()
                 vals.update(v)
@@ -1077,9 +1078,9 @@ class InstanceStyleDStep(CapturedStep):
             # the first form of this schedule died exactly so.)
             tokens = parallel.exchange_in_buckets(params, self._buckets, [grads["s"], grads["t"]], (marks["s"], marks["t"]), main)
             parallel.finish_buckets(tokens)
-            ops.join(main, s_src, s_tgt)
+            launch.join(main, s_src, s_tgt)
         else:
-            ops.join(main, s_src, s_tgt)
+            launch.join(main, s_src, s_tgt)
             both = [(a, b) for a, b in zip(grads["s"], grads["t"]) if a is not None and b is not None]
             if both:
                 torch._foreach_add_([a for a, _ in both], [b for _, b in both])

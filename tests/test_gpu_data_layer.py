@@ -82,7 +82,7 @@ def test_sgg_captured_step_consumes_loader_batches_of_varying_size(small_cfg, mo
     stream (I2V_UPLOAD_STREAM=0).  Round 3 met a host segfault in hipGraphLaunch in exactly this test, in exactly this file order
     (tests/test_gpu_configs.py first), with the copy stream on, and switched it off by default.  Since then (a) no graph is dropped while a replay of it may still be running
     (capacity growth in stage() dropped every graph right behind an asynchronous replay -- ``invalidate_graphs`` synchronises
-    first now) and (b) the copy stream is a stream of its own (ops.role_stream) instead of the next of torch's 32 pooled handles.
+    first now) and (b) the copy stream is a stream of its own (launch.role_stream) instead of the next of torch's 32 pooled handles.
     DESIGN.md 5.5 has the analysis.
 
     SGG_emb: 8 loader minibatches of 2 frames in >= 3 sizes, 4-32 boxes and 2-32 pairs per frame, through (a) the eager
@@ -90,7 +90,7 @@ def test_sgg_captured_step_consumes_loader_batches_of_varying_size(small_cfg, mo
     frame size, extent of the maps read on the device): the same per-batch losses (1e-3; measured ~1e-6) and the same
     weights, with the lag of the pipeline (two calls: the backbone beside the head is cut by stage)."""
     small_cfg()
-    from i2vsgg_amd import ops, train
+    from i2vsgg_amd import launch, train
     monkeypatch.setenv("I2V_UPLOAD_STREAM", "1" if copy_stream else "0")
     imdb, dl = _loader("synthetic_20_v", 2, seed=3)
     rels = imdb.gt_rels(62)
@@ -141,7 +141,7 @@ def test_sgg_captured_step_consumes_loader_batches_of_varying_size(small_cfg, mo
     assert (step._uploader.stream is not None) == copy_stream
     if copy_stream and os.environ.get("I2V_ALIAS_REPRO") != "1":       # tools/alias_repro.py undoes the role streams on purpose
         dev = torch.device(DEV)
-        table = ops.stream_table()
+        table = launch.stream_table()
         assert step._uploader.stream.cuda_stream == table[(dev.index, "copy", 0)]
         assert len(set(table.values())) == len(table)            # no role shares a handle with another
         cap = getattr(torch.cuda.graph, "default_capture_stream", None)

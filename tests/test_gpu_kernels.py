@@ -1270,14 +1270,14 @@ def test_filter_gradient_lds_dma_staging_is_bit_equal(B, C, N, H, W):
     order per accumulator as the register-staged kernel: the SAME BITS with ordered sums, for every tile shape, on channel counts
     that leave partial tiles (72, 196), pixel counts that leave a partial last stage, and the 36-plane batched form the Winograd
     filter gradient uses; both within 1e-5 of float64 torch."""
-    from i2vsgg_amd import ops
+    from i2vsgg_amd import launch, ops
     from i2vsgg_amd._lib import TUNE, lib
     torch.manual_seed(11)
     cl = lambda t: t.contiguous(memory_format=torch.channels_last)
     x, g = cl(torch.randn(B, C, H, W, device=DEV)), cl(torch.randn(B, N, H, W, device=DEV))
     want = torch.nn.grad.conv2d_weight(x.double(), (N, C, 1, 1), g.double(), 1, 0)
     scale = float(want.abs().max())
-    ctx = ops.LaunchContext(DEV, ordered=True)
+    ctx = launch.LaunchContext(DEV, ordered=True)
     keys = [TUNE["I2V_WGRAD_DMA"], TUNE["I2V_WGRAD_V2"]]
     old = [lib.i2v_get_tuning(k) for k in keys]
     assert old[0] == 1                                      # the default

@@ -563,7 +563,7 @@ def test_sgg_step_back_to_back_replays_are_ordered(cfg, monkeypatch):
     forward read and produced (``SGGEmbStep.trace``: loss, feature maps, scores, embedding, an RNG canary drawn from the
     dropout generator, fc7 / fc6 weights, boxes, labels).  A deviation is reported as (first step, first column) -- round 2
     saw ONE final loss off by 5.9e-5 with an abs-sum of the weights that could not say where it came from."""
-    from i2vsgg_amd import ops, train
+    from i2vsgg_amd import launch, train
     n = 20
     # The default-stream runs below go through train.replay_graph's redirect (a private stream between two event edges),
     # whatever DEBUG_CLR_GRAPH_PACKET_CAPTURE says: the variable is no proof of what the runtime read (round-3 advice), so the
@@ -623,7 +623,7 @@ def test_sgg_step_back_to_back_replays_are_ordered(cfg, monkeypatch):
         assert bool(train._REPLAY_STREAMS) == (not own)
     h = train._REPLAY_STREAMS[torch.device(DEV).index].cuda_stream
     assert h != torch.cuda.default_stream(torch.device(DEV)).cuda_stream
-    assert h == ops.stream_table()[(torch.device(DEV).index, "replay", 0)]
+    assert h == launch.stream_table()[(torch.device(DEV).index, "replay", 0)]
 
 
 def test_sgg_step_staged_batches_meet_their_features(cfg):
@@ -1076,76 +1076,76 @@ def test_rccl_rehearsal_of_the_plain_data_parallel_exchanges(cfg, monkeypatch, w
 
 def test_fork_inside_a_graph_branch_is_an_error_not_a_crash():
     """Round-2 review: a fork made inside a forked branch ends hipStreamEndCapture in a host segfault on ROCm 7.2, and the
-    step objects avoided it by construction only.  They fork through ``ops.branch`` now, which refuses the nested fork while a
+    step objects avoided it by construction only.  They fork through ``launch.branch`` now, which refuses the nested fork while a
     capture is running (and is an ordinary fork / join outside one)."""
-    from i2vsgg_amd import ops
-    s1, s2 = ops.role_stream(DEV, ("frame", 0)), ops.role_stream(DEV, ("frame", 1))
+    from i2vsgg_amd import launch
+    s1, s2 = launch.role_stream(DEV, ("frame", 0)), launch.role_stream(DEV, ("frame", 1))
     x = torch.ones(1024, device=DEV)
     torch.cuda.synchronize()
     g, caught = torch.cuda.CUDAGraph(), []
     with torch.cuda.graph(g):
         main = torch.cuda.current_stream()
-        with ops.branch(s1, main):
+        with launch.branch(s1, main):
             y = x * 2
             try:
-                with ops.branch(s2, s1):
+                with launch.branch(s2, s1):
                     y = y + 1
             except RuntimeError as e:
                 caught.append(str(e))
-        ops.join(main, s1)
+        launch.join(main, s1)
         z = y + 1
     g.replay()
     torch.cuda.synchronize()
     assert caught and "fork inside a forked graph branch" in caught[0]
     assert float(z[0]) == 3.0
     main = torch.cuda.current_stream()              # outside a capture nesting is an ordinary (if pointless) fork / join
-    with ops.branch(s1, main):
-        with ops.branch(s2, s1):
+    with launch.branch(s1, main):
+        with launch.branch(s2, s1):
             w = x + 5
-        ops.join(s1, s2)
-    ops.join(main, s1)
+        launch.join(s1, s2)
+    launch.join(main, s1)
     torch.cuda.synchronize()
     assert float(w[0]) == 6.0
 
 
 def test_branch_streams_never_alias(cfg):
     """Round-3 review: torch.cuda.Stream() deals 32 pooled handles round robin, so after a few step objects a "copy" or branch
-    stream could BE the stream a later capture forks or captures on.  The step objects take their streams from ops.role_stream:
+    stream could BE the stream a later capture forks or captures on.  The step objects take their streams from launch.role_stream:
     one HIP stream per role, created once per process by the library, distinct from each other and from every pooled handle;
-    ops.branch refuses an alias of the forking stream or of an open sibling."""
-    from i2vsgg_amd import ops, train
+    launch.branch refuses an alias of the forking stream or of an open sibling."""
+    from i2vsgg_amd import launch, train
     dev = torch.device(DEV)
     pooled = {torch.cuda.Stream(dev).cuda_stream for _ in range(40)}          # the whole pool, dealt round robin
     assert len(pooled) <= 32
     pooled |= {torch.cuda.default_stream(dev).cuda_stream, torch.cuda.current_stream(dev).cuda_stream}
     net = train.build_sgg_net(layers=50, seed=5, device=DEV)
     steps = [train.SGGEmbStep(net, 2, seed=3, device=DEV, h=200, w=320, n_boxes=6, n_pairs=5) for _ in range(3)]
-    table = ops.stream_table()
+    table = launch.stream_table()
     handles = list(table.values())
     assert len(set(handles)) == len(handles) and not (set(handles) & pooled), table
     for a in steps[1:]:                                  # objects share the registry's streams instead of drawing new ones
         assert [t.cuda_stream for t in a._frame_streams] == [t.cuda_stream for t in steps[0]._frame_streams]
-    assert ops.role_stream(dev, ("frame", 0)) is ops.role_stream(dev, ("frame", 0))
+    assert launch.role_stream(dev, ("frame", 0)) is launch.role_stream(dev, ("frame", 0))
     for st in steps:
         st.opt.unfuse()
-    main = ops.role_stream(dev, "warmup")                # (ExternalStream(0) would draw a pooled stream, so not the default stream)
+    main = launch.role_stream(dev, "warmup")                # (ExternalStream(0) would draw a pooled stream, so not the default stream)
     with torch.cuda.stream(main):
         alias = torch.cuda.ExternalStream(main.cuda_stream, device=dev)
         assert alias.cuda_stream == main.cuda_stream
         with pytest.raises(RuntimeError, match="IS the forking stream"):
-            with ops.branch(alias, main):
+            with launch.branch(alias, main):
                 pass
-        s1 = ops.role_stream(dev, ("frame", 0))
+        s1 = launch.role_stream(dev, ("frame", 0))
         twin = torch.cuda.ExternalStream(s1.cuda_stream, device=dev)
-        with ops.branch(s1, main):
+        with launch.branch(s1, main):
             pass
         with pytest.raises(RuntimeError, match="already an open branch"):
-            with ops.branch(twin, main):
+            with launch.branch(twin, main):
                 pass
-        ops.join(main, s1)
-        with ops.branch(twin, main):                     # joined: the handle is free again
+        launch.join(main, s1)
+        with launch.branch(twin, main):                     # joined: the handle is free again
             pass
-        ops.join(main, twin)
+        launch.join(main, twin)
     torch.cuda.synchronize()
 
 

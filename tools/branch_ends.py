@@ -12,7 +12,7 @@ sys.path.insert(0, ROOT)
 os.environ.setdefault("DEBUG_CLR_GRAPH_PACKET_CAPTURE", "0")
 import torch  # noqa: E402
 
-from i2vsgg_amd import ops, train  # noqa: E402
+from i2vsgg_amd import launch, train  # noqa: E402
 from i2vsgg_amd._lib import lib  # noqa: E402
 
 DEV = torch.device("cuda:0")
@@ -35,7 +35,7 @@ def _event(enable_timing=True):
     return Stamp()
 
 
-real_join, real_enter = ops.join, ops.branch.__enter__
+real_join, real_enter = launch.join, launch.branch.__enter__
 
 
 def enter(self):
@@ -62,8 +62,8 @@ def join(origin, *streams):
         marks["joined"] = e
 
 
-ops.branch.__enter__ = enter
-ops.join = join
+launch.branch.__enter__ = enter
+launch.join = join
 sizes = [tuple(int(v) for v in a.split("x")) for a in sys.argv[1:] if "x" in a] or [(600, 1000)]
 for h, w in sizes:
     marks.clear()

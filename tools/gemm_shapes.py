@@ -10,7 +10,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 os.environ.setdefault("DEBUG_CLR_GRAPH_PACKET_CAPTURE", "0")
 import torch  # noqa: E402
 
-from i2vsgg_amd import ops  # noqa: E402
+from i2vsgg_amd import launch, ops  # noqa: E402
 from i2vsgg_amd._lib import lib  # noqa: E402
 
 DEV = "cuda:0"
@@ -85,7 +85,7 @@ for name, M, K, N, res, reps in cases:
         w = torch.rand(N, K, 1, 1, device=DEV) * 2 - 1
         sc, sh = torch.rand(N, device=DEV) + 0.5, torch.rand(N, device=DEV)
         r = torch.randn(M, N, 1, 1, device=DEV) if res else None
-        ctx = ops.LaunchContext(DEV, ordered="ordered" in name)
+        ctx = launch.LaunchContext(DEV, ordered="ordered" in name)
         ops_.append((x, w, sc, sh, r, ctx))
 
     def make(c):

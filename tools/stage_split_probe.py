@@ -13,7 +13,7 @@ os.environ.setdefault("DEBUG_CLR_GRAPH_PACKET_CAPTURE", "0")
 import torch  # noqa: E402
 
 import bench  # noqa: E402
-from i2vsgg_amd import ops, train  # noqa: E402
+from i2vsgg_amd import launch, train  # noqa: E402
 
 DEV = torch.device("cuda:0")
 cuts = [int(a) for a in sys.argv[1:]] or [6, 7, 8]
@@ -30,7 +30,7 @@ for cut in cuts:
         mid_shape = base.forward_front(fs.im, cut).shape
     mk = lambda: torch.zeros(mid_shape, device=DEV).contiguous(memory_format=torch.channels_last)
     mid_next, mid_cur = mk(), mk()
-    ctxA, ctxB = ops.LaunchContext(DEV), ops.LaunchContext(DEV)
+    ctxA, ctxB = launch.LaunchContext(DEV), launch.LaunchContext(DEV)
     for _ in range(2):
         with ctxA, torch.no_grad():
             base.forward_front(fs.im, cut, out=mid_next)
@@ -45,12 +45,12 @@ for cut in cuts:
         step._rotate()
         step.fmap_head_flat.copy_(step.fmap_flat)
         mid_cur.copy_(mid_next)
-        with ops.branch(sA, main), ctxA, torch.no_grad():
+        with launch.branch(sA, main), ctxA, torch.no_grad():
             base.forward_front(fs.im, cut, out=mid_next)
-        with ops.branch(sB, main), ctxB, torch.no_grad():
+        with launch.branch(sB, main), ctxB, torch.no_grad():
             base.forward_back(mid_cur, cut, out=step._fmap_dst(fs))
         step._head()
-        ops.join(main, sA, sB)
+        launch.join(main, sA, sB)
 
     g = torch.cuda.CUDAGraph()
     torch.cuda.synchronize()
@@ -60,13 +60,13 @@ for cut in cuts:
     print("stage split, cut %2d: %.3f ms per step (%.1f frames/s)   loss %.6f" % (cut, ms, 2e3 / ms, float(step.loss)))
     del g
 # four chains: head | stem .. layer3[:c1] | layer3[c1:c2] | layer3[c2:]
-sC = ops.role_stream(DEV, "side")
+sC = launch.role_stream(DEV, "side")
 for c1, c2 in ((3, 13), (4, 13), (5, 14)):
     with torch.no_grad():
         m1 = base.forward_front(fs.im, c1)
     mk = lambda t: torch.zeros(t.shape, device=DEV).contiguous(memory_format=torch.channels_last)
     a_next, a_cur, b_next, b_cur = mk(m1), mk(m1), mk(m1), mk(m1)
-    ctxs = [ops.LaunchContext(DEV) for _ in range(3)]
+    ctxs = [launch.LaunchContext(DEV) for _ in range(3)]
     parts = [lambda: base.forward_front(fs.im, c1, out=a_next), lambda: base.forward_back(a_cur, c1, out=b_next, end=c2),
              lambda: base.forward_back(b_cur, c2, out=step._fmap_dst(fs))]
     for _ in range(2):
@@ -82,10 +82,10 @@ for c1, c2 in ((3, 13), (4, 13), (5, 14)):
         step.fmap_head_flat.copy_(step.fmap_flat)
         a_cur.copy_(a_next); b_cur.copy_(b_next)
         for st, ctx, part in zip((sA, sB, sC), ctxs, parts):
-            with ops.branch(st, main), ctx, torch.no_grad():
+            with launch.branch(st, main), ctx, torch.no_grad():
                 part()
         step._head()
-        ops.join(main, sA, sB, sC)
+        launch.join(main, sA, sB, sC)
 
     g = torch.cuda.CUDAGraph()
     torch.cuda.synchronize()

@@ -9,7 +9,7 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 
-from i2vsgg_amd import ops  # noqa: E402
+from i2vsgg_amd import launch, ops  # noqa: E402
 from i2vsgg_amd._lib import TUNE, lib  # noqa: E402
 
 DEV = "cuda:0"
@@ -51,7 +51,7 @@ for name, B, H, W, C, N in cases:
         lib.i2v_set_tuning(TUNE["I2V_WGRAD_V2"], tiles)
         for dma in (0, 1):
             lib.i2v_set_tuning(TUNE["I2V_WGRAD_DMA"], dma)
-            ctx = ops.LaunchContext(DEV, ordered=True)
+            ctx = launch.LaunchContext(DEV, ordered=True)
 
             def fn2():
                 with ctx, torch.no_grad():
@@ -61,7 +61,7 @@ for name, B, H, W, C, N in cases:
                                                                          "LDS-DMA" if dma else "registers", t, fl / t / 1e6), flush=True)
     lib.i2v_set_tuning(TUNE["I2V_WGRAD_V2"], 1)
     for ordered in (False, True):
-        ctx = ops.LaunchContext(DEV, ordered=ordered)
+        ctx = launch.LaunchContext(DEV, ordered=ordered)
         for dma in (0, 1):
             assert lib.i2v_set_tuning(TUNE["I2V_WGRAD_DMA"], dma) == 0
 
