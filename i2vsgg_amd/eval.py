@@ -16,6 +16,7 @@ import torch
 from . import launch, ops
 from .graphs import GraphRecorder, replay_graph
 from .model.utils.config import cfg
+from .staging import _Slot, _place_u8, parse_u8_meta, place_frames, step_uploader
 
 
 class _FrameShape:
@@ -64,32 +65,17 @@ class _FrameGraphStep(GraphRecorder):
         self._staged = key
         return fs
 
-    def _place(self, fs, im_data):
-        n, c = im_data.shape[:2]
-        if c == 4:
-            fs.im[:n].copy_(im_data, non_blocking=True)
-        else:
-            fs.im[:n, :3].copy_(im_data, non_blocking=True)      # NCHW3 -> NHWC4 (channel 3 stays zero)
-
-    def _place_u8(self, frames_u8, meta):
+    def _place_u8(self, frames_u8, rows, size):
         """The device front-end of ``roibatchLoader(training=False, device_prep=True)`` items: uint8 frames as decoded cross PCIe,
-        BGR swap / mean subtraction / resize run in ``i2v_image_prep``.  ``meta`` rows: [flipped, canvas_h, canvas_w, scale,
-        target]; the frames of a call share their canvas.  -> (frame set, the (n,3) im_info rows)."""
-        from .staging import _Uploader, _place_u8
-        meta = np.asarray(meta.cpu() if torch.is_tensor(meta) else meta, np.float64).reshape(-1, 5)
+        BGR swap / mean subtraction / resize run in ``i2v_image_prep``.  ``rows``, ``size``: ``staging.parse_u8_meta`` of the
+        items' meta.  -> the frame set."""
         n = len(frames_u8)
-        if n > self.frames or len(meta) != n:
-            raise ValueError("%s.stage_u8: %d frames / %d meta rows, the step was built for %d" % (type(self).__name__, n, len(meta), self.frames))
-        sizes = {(int(m[1]), int(m[2])) for m in meta}
-        if len(sizes) != 1:
-            raise ValueError("stage_u8: the frames of one call must share their resized size, got %s" % sorted(sizes))
-        (H, W), = sizes
-        fs = self._shape(H, W)
-        if getattr(self, "_uploader", None) is None:
-            self._uploader = _Uploader(self.dev)
-        frames_u8 = [f.reshape(f.shape[-3:]) for f in frames_u8]              # (1,H,W,3) items of a batch_size-1 loader
-        _place_u8(self._uploader, frames_u8, meta, fs.im[:n])
-        return fs, np.array([[m[1], m[2], m[3]] for m in meta], np.float32)
+        if n > self.frames or len(rows) != n or size is None:
+            raise ValueError("%s.stage_u8: %d frames / %d meta rows of canvas %s, the step was built for %d"
+                             % (type(self).__name__, n, len(rows), size, self.frames))
+        fs = self._shape(*size)
+        _place_u8(step_uploader(self), frames_u8, rows, fs.im[:n])
+        return fs
 
     def invalidate_graphs(self):
         """Drop every captured graph (they are captured again on first use).  Needed after the network's weights change: a
@@ -187,14 +173,15 @@ class DetectStep(_FrameGraphStep):
         if n > self.frames:
             raise ValueError("DetectStep.stage: %d frames, the step was built for %d" % (n, self.frames))
         fs = self._shape(H, W)
-        self._place(fs, im_data)
+        place_frames(fs.im, im_data)
         self._set_info(im_info, n)
         return fs
 
     def stage_u8(self, frames_u8, meta):
         """The same from ``roibatchLoader(training=False, device_prep=True)`` items: a list of uint8 (H,W,3) frames and their
         meta rows (``_place_u8``)."""
-        fs, info = self._place_u8(frames_u8, meta)
+        rows, size, info = parse_u8_meta(meta)
+        fs = self._place_u8(frames_u8, rows, size)
         self._set_info(info, len(frames_u8))
         return fs
 
@@ -241,7 +228,6 @@ class RelationStep(_FrameGraphStep):
         self._alloc(int(cap_boxes))
 
     def _alloc(self, cap_boxes):
-        from .staging import _Slot
         F_, cb = self.frames, max(int(cap_boxes), 3)
         cp = (cb - 1) * (cb - 2)
         self.cap_boxes, self.cap_pairs = cb, cp
@@ -275,17 +261,16 @@ class RelationStep(_FrameGraphStep):
             raise ValueError("RelationStep.stage: %d frames / %d paths, the step was built for %d" % (n, len(im_paths), self.frames))
         self._stage_pairs(im_info, im_paths)
         fs = self._shape(H, W)
-        self._place(fs, im_data)
+        place_frames(fs.im, im_data)
         return fs
 
     def stage_u8(self, frames_u8, meta, im_paths):
         """The same from ``roibatchLoader(training=False, device_prep=True)`` items (``_place_u8``)."""
         if len(im_paths) != len(frames_u8):
             raise ValueError("RelationStep.stage_u8: %d frames / %d paths" % (len(frames_u8), len(im_paths)))
-        m = np.asarray(meta.cpu() if torch.is_tensor(meta) else meta, np.float64).reshape(-1, 5)
-        self._stage_pairs(np.array([[r[1], r[2], r[3]] for r in m], np.float32), im_paths)     # im_info as the host form holds it (fp32); may grow the capacity
-        fs, _ = self._place_u8(frames_u8, meta)
-        return fs
+        rows, size, info = parse_u8_meta(meta)
+        self._stage_pairs(info, im_paths)          # im_info as the host form holds it (fp32); may grow the capacity
+        return self._place_u8(frames_u8, rows, size)
 
     def _stage_pairs(self, im_info, im_paths):
         from .model.faster_rcnn.faster_rcnn_SGG_emb import build_eval_pair_tables

@@ -172,6 +172,42 @@ class _Uploader:
         ring["free"][i] = ev
 
 
+def step_uploader(step):
+    """The uploader of a step object, created on first use: one per step, so the frames of one step share one ring."""
+    if getattr(step, "_uploader", None) is None:
+        step._uploader = _Uploader(step.dev)
+    return step._uploader
+
+
+def place_frames(dst, frames, owner=None):
+    """A minibatch of n frames into the first n of ``dst`` (.., 4, H, W) channels_last, on the caller's stream: the (n,4,H,W)
+    blob of the device front-end by a plain copy, (n,3,H,W) float frames by ONE strided copy NCHW3 -> NHWC4 (channel 3 stays
+    zero).  Host frames cross PCIe through the uploader of the step ``owner`` (the copy stream, beside the running step) when
+    one is given, else directly on the caller's stream (pinned memory asynchronously)."""
+    n, c = frames.shape[:2]
+    dst = dst[:n] if c == 4 else dst[:n, :3]
+    if frames.is_cuda or owner is None:
+        dst.copy_(frames, non_blocking=True)
+    else:
+        uploader = step_uploader(owner)
+        src, token = uploader.upload(frames.float())
+        dst.copy_(src)
+        uploader.consumed(token)
+
+
+def parse_u8_meta(meta):
+    """The meta rows [flipped, canvas_h, canvas_w, scale, target] of a ``roibatchLoader(device_prep=True)`` minibatch ->
+    (rows (n,5) float64, (H, W), im_info (n,3) float32 rows [H, W, scale]).  The frames of one call share their canvas
+    (ValueError otherwise); (H, W) is None for a canvas <= 0, a minibatch the device front-end does not take (the square trim:
+    the host form stages it)."""
+    rows = np.asarray(meta.cpu() if torch.is_tensor(meta) else meta, np.float64).reshape(-1, 5)
+    sizes = {(int(m[1]), int(m[2])) for m in rows}
+    if len(sizes) != 1:
+        raise ValueError("the frames of one call must share their resized size, got %s" % sorted(sizes))
+    (H, W), = sizes
+    return rows, ((H, W) if H > 0 and W > 0 else None), rows[:, 1:4].astype(np.float32)
+
+
 def _place_u8(uploader, frames_u8, meta, dst):
     """The device front-end of a ``roibatchLoader(device_prep=True)`` minibatch: every decoded uint8 frame crosses PCIe as it
     is (copy stream) and ``i2v_image_prep`` writes the mean-subtracted, resized BGR image into its slot of ``dst`` (n,4,H,W)
@@ -179,6 +215,6 @@ def _place_u8(uploader, frames_u8, meta, dst):
     dst.zero_()
     for f, u8 in enumerate(frames_u8):
         flipped, target = bool(meta[f][0]), int(meta[f][4])
-        src, token = uploader.upload(u8)
+        src, token = uploader.upload(u8.reshape(u8.shape[-3:]))          # (1,H,W,3): an item of a batch_size-1 loader
         ops.image_prep(src, cfg.PIXEL_MEANS, target, flipped=flipped, rgb=True, blob=dst[f:f + 1])
         uploader.consumed(token)

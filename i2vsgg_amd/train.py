@@ -18,7 +18,8 @@ from . import synthetic as syn
 from .graphs import CapturedStep, replay_graph, _REPLAY_STREAMS                                   # noqa: F401
 from .model.utils.config import cfg
 from .optim import FusedSGD, FusedAdam, make_optimizer, _same_memory_order                       # noqa: F401
-from .staging import _Slot, _Uploader, _place_u8, synthetic_sgg_batch, sgg_head_inputs, _rasterize_host    # noqa: F401
+from .staging import (_Slot, _place_u8, parse_u8_meta, place_frames, step_uploader, synthetic_sgg_batch,      # noqa: F401
+                      sgg_head_inputs, _rasterize_host)
 
 
 class _FrameSet:
@@ -177,7 +178,6 @@ class SGGEmbStep(CapturedStep):
         self.cap_cells = 0
         self.fmap_flat = self.fmap_head_flat = None
         self.cur = self.inp = None    # head inputs: ``inp`` is written by stage(), ``cur`` read by the head
-        self._uploader = None
         self._staged = None           # key of the frame set staged last
         self._fmap_key = None         # key of the frame set whose features ``fmap_flat`` holds
         self.primed = False
@@ -287,16 +287,8 @@ class SGGEmbStep(CapturedStep):
         fs = self._frames(key)
         if placer is not None:
             placer(fs)
-        elif frames.shape[1] == 4 and frames.is_cuda:
-            fs.im.copy_(frames)
-        elif frames.is_cuda:
-            fs.im[:, :3].copy_(frames)                           # NCHW3 -> NHWC4 (channel 3 stays zero): one strided copy
-        else:                                                    # host frames: PCIe on the copy stream, beside the running step
-            if self._uploader is None:
-                self._uploader = _Uploader(self.dev)
-            src, token = self._uploader.upload(frames)
-            fs.im[:, :3].copy_(src)
-            self._uploader.consumed(token)
+        else:
+            place_frames(fs.im, frames, self)
         self.info = np.asarray(info, np.float32).reshape(-1, 3) if not torch.is_tensor(info) else info.detach().cpu().numpy().reshape(-1, 3)
         nb, npair = fields["boxes"].shape[0], fields["relb"].shape[0]
         self.n_rows = nb + npair
@@ -381,18 +373,15 @@ class SGGEmbStep(CapturedStep):
         Same contract as ``stage_batch`` otherwise; a minibatch the device front-end does not take (the square trim) -> False."""
         if not isinstance(data, (list, tuple)) or len(data) <= 2:
             return False
-        frames, meta = data[0], data[1].numpy()
-        if int(meta[0][1]) <= 0 or int(meta[0][2]) <= 0:
+        frames = data[0]
+        rows, size, info = parse_u8_meta(data[1])
+        if size is None:
             return False
-        hc, wc = int(meta[0][1]), int(meta[0][2])
-        info = np.array([[hc, wc, m[3]] for m in meta], np.float32)
         rels = self.net.vrd.source_gt_rels
         fields = sgg_head_inputs([rels.get(str(p).split("/")[-1]) for p in data[4]], info, self.net.vrd.n_rel)
         if fields is None:
             return False
-        if self._uploader is None:
-            self._uploader = _Uploader(self.dev)
-        self.stage(lambda fs: _place_u8(self._uploader, frames, meta, fs.im), info, fields, size=(len(frames), hc, wc))
+        self.stage(lambda fs: _place_u8(step_uploader(self), frames, rows, fs.im), info, fields, size=(len(frames),) + size)
         return True
 
     def reseed(self, seed):
@@ -847,7 +836,6 @@ class InstanceStyleDStep(CapturedStep):
         self._branch_streams = [launch.role_stream(self.dev, ("domain", i)) for i in range(2)] if self.branches else []
         self.sets, self.max_graphs, self._tick, self._pool = {}, int(max_graphs), 0, None
         self._cur = None              # the _DomainSet staged last
-        self._uploader = None
         self._graphs_on = False
         mg = int(cfg.MAX_NUM_GT_BOXES)
         self.info = torch.zeros((n_frames, 3), device=self.dev)        # shared by every size: a captured step reads them
@@ -914,14 +902,8 @@ class InstanceStyleDStep(CapturedStep):
         for k, (dst, src) in enumerate(((ds.im_s, im_s), (ds.im_t, im_t))):
             if placers is not None:                              # the device front-end writes the frames itself (_place_u8)
                 placers[k](dst)
-            elif src.is_cuda:
-                dst[:, :3].copy_(src)
-            else:                                                # host frames: PCIe on the copy stream, beside the running step
-                if self._uploader is None:
-                    self._uploader = _Uploader(self.dev)
-                dev3, token = self._uploader.upload(src.float() if src.dtype != torch.float32 else src)
-                dst[:, :3].copy_(dev3)
-                self._uploader.consumed(token)
+            else:
+                place_frames(dst, src, self)
         cp(self.info, info); cp(self.info_t, info_t); cp(self.gt, gt); cp(self.nb, nb)
         if ds.im_st is not None:
             ds.im_st[:n].copy_(ds.im_s); ds.im_st[n:].copy_(ds.im_t)
@@ -929,19 +911,15 @@ class InstanceStyleDStep(CapturedStep):
     def stage_batch_u8(self, data_s, data_t):
         """The same with ``roibatchLoader(device_prep=True)`` minibatches (``collate_device_prep``): uint8 frames, the image work
         on the device.  False when either minibatch cannot go that way (the square trim) or would be skipped."""
-        ok = lambda d: isinstance(d, (list, tuple)) and len(d) >= 4 and int(d[1][0][1]) > 0 and int(d[1][0][2]) > 0
-        if not ok(data_s) or not ok(data_t):
+        if not all(isinstance(d, (list, tuple)) and len(d) >= 4 for d in (data_s, data_t)):
             return False
-        ms, mt = data_s[1].numpy(), data_t[1].numpy()
-        info = torch.tensor([[m[1], m[2], m[3]] for m in ms], dtype=torch.float32)
-        info_t = torch.tensor([[m[1], m[2], m[3]] for m in mt], dtype=torch.float32)
-        n = len(data_s[0])
-        key_shapes = (torch.empty((n, 0, int(ms[0][1]), int(ms[0][2]))), torch.empty((n, 0, int(mt[0][1]), int(mt[0][2]))))
-        if self._uploader is None:
-            self._uploader = _Uploader(self.dev)
-        self.stage(key_shapes[0], info, data_s[2], data_s[3], key_shapes[1], info_t,
-                   placers=(lambda dst: _place_u8(self._uploader, data_s[0], ms, dst),
-                            lambda dst: _place_u8(self._uploader, data_t[0], mt, dst)))
+        (ms, size_s, info), (mt, size_t, info_t) = parse_u8_meta(data_s[1]), parse_u8_meta(data_t[1])
+        if size_s is None or size_t is None:
+            return False
+        n, up = len(data_s[0]), step_uploader(self)
+        self.stage(torch.empty((n, 0) + size_s), torch.from_numpy(info), data_s[2], data_s[3], torch.empty((n, 0) + size_t),
+                   torch.from_numpy(info_t), placers=(lambda dst: _place_u8(up, data_s[0], ms, dst),
+                                                      lambda dst: _place_u8(up, data_t[0], mt, dst)))
         return True
 
     def stage_batch(self, data_s, data_t):

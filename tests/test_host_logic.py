@@ -544,3 +544,21 @@ def test_sampled_rois_are_shaped_like_the_samplers_output(B, R):
         assert len({int(i) for i in rpn.iou_matrix(r[:n_fg, 1:], gt[b]).argmax(1)}) >= 4      # several clusters, not one
     assert not np.array_equal(syn.sampled_rois(5, B, H, W, R), syn.sampled_rois(6, B, H, W, R))
     assert np.array_equal(syn.sampled_rois(5, B, H, W, R), rois)
+
+
+def test_u8_meta_rows_are_parsed_in_one_place():
+    """staging.parse_u8_meta: rows [flipped, canvas_h, canvas_w, scale, target] -> (rows, (H, W), im_info fp32 [H, W, scale]); a
+    mixed-size minibatch is an error, a canvas <= 0 (the square trim) has no size."""
+    import torch
+    from i2vsgg_amd.staging import parse_u8_meta
+    meta = torch.tensor([[1.0, 192, 342, 0.4, 192], [0.0, 192, 342, 0.26666668, 192]], dtype=torch.float64)
+    rows, size, info = parse_u8_meta(meta)
+    assert rows.shape == (2, 5) and rows.dtype == np.float64 and bool(rows[0][0]) and not bool(rows[1][0])
+    assert size == (192, 342) and info.dtype == np.float32
+    assert np.array_equal(info, np.array([[192, 342, 0.4], [192, 342, 0.26666668]], np.float32))
+    assert parse_u8_meta(meta[0].numpy())[1] == (192, 342)                       # one row, as a batch_size-1 loader hands it over
+    with pytest.raises(ValueError, match="share their resized size"):
+        parse_u8_meta(torch.tensor([[0.0, 192, 342, 0.4, 192], [0.0, 192, 320, 0.4, 192]], dtype=torch.float64))
+    for bad in ([0.0, 0, 0, 0.4, 192], [0.0, 192, -1, 0.4, 192]):
+        rows, size, info = parse_u8_meta(np.array([bad, bad]))
+        assert size is None and info.shape == (2, 3)
