@@ -45,6 +45,8 @@ SIGNATURES = {
     "i2v_conv_fwd": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _z, _p]),
     "i2v_conv_fwd_splits": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _i, _z]),
     "i2v_conv_split_workspace_bytes": (_z, [_i, _i, _i, _i, _i, _i, _i, _i, _i]),
+    "i2v_conv_fwd_plan": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _z, _p, _i]),
+    "i2v_conv_wgrad_plan": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _z, _p, _i]),
     "i2v_set_tuning": (_i, [_i, _i]),
     "i2v_get_tuning": (_i, [_i]),
     "i2v_gemm_nt_batched": (_i, [_p, _p, _p, _i, _i, _i, _i, _l, _l, _l, _p, _z, _p]),

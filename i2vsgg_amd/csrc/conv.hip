@@ -14,9 +14,12 @@
 // free.  K order inside a 8-deep step is permuted (lane half h owns k = 4h..4h+3) so a
 // fragment is ONE b128 read; A and B use the same permutation, so the sum is unchanged.
 #include "common.h"
+#include "conv_plan.h"
 #include <algorithm>
 #include <type_traits>
 #include <stdlib.h>
+
+using namespace convplan;
 
 namespace {
 
@@ -27,11 +30,8 @@ typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 constexpr int BK = 16;          // k per LDS stage of the wgrad kernel
-constexpr int KTAB_MAX = 2560;  // filter-tap table entries (K/4): KH*KW*Cin <= 10240 for non-1x1 filters
-constexpr int BKS = 32;         // k per LDS stage of the forward/dgrad kernel (= floats per LDS row)
 constexpr int LDS_ROW = 20;     // floats per staged row (16 + 4 pad)
 constexpr int THREADS = 256;
-constexpr int kSplitInKernelMax = 4;   // most splits the in-kernel split-K finish sums (else: atomics)
 
 struct ConvP {
     const float* x; const float* w; const float* scale; const float* shift; const float* res; float* y;
@@ -44,11 +44,11 @@ struct ConvP {
     int ostride;                 // output pixel stride (dgrad of strided 1x1): y is (B,Ho*os..,Wo*os..,N)
     int Hy, Wy;                  // spatial size of the y buffer
     int lgCin;                   // log2(Cin) if power of two else -1
-    int force_tile;              // >=0: tile config override (tuning / tests), -1: cost model
+    int reserved0;               // unused (held the forced tile index; kept so that the argument offsets stay)
     unsigned x_bytes, w_bytes;   // sizes of x and w for the buffer descriptors (< 2 GiB each)
     int ablate;                  // diagnostic (i2v_conv_set_tile bits 10-11): 1 = skip staging in the K loop, 2 = skip MFMAs
     int ktab_entries;            // tap-table entries in LDS (>= 1; K/4 rounded up to whole stages for KxK filters)
-    int dry;                     // plan only: run_conv returns the chosen split-K factor instead of launching
+    int reserved1;               // unused (held the plan-only mode; kept so that the argument offsets stay)
     unsigned long long* clk;     // diagnostic only (i2v_conv_debug_clock): per-workgroup {shader cycles, 100 MHz ticks}
     float* ws;                   // split-K partial tiles [split][tile][BM*BN] (nullptr: fp32 atomics into y)
     int* cnt;                    // split-K arrival counters, one per tile, zero between launches
@@ -1049,41 +1049,53 @@ inline int ilog2_exact(int v) {
     return l;
 }
 
-constexpr int NUM_CU = 256;
 int g_force_tile = -1;           // i2v_conv_set_tile(): tuning hook (the tile index)
 int g_ablate = 0;
 unsigned long long* g_clk = nullptr;   // i2v_conv_debug_clock()
-// Tuning knobs live in g_i2v_tuning (i2v_set_tuning; the library itself reads no environment variable).
-// SPLIT_TARGET (workgroups per CU a split-K launch aims for), measured inside the step: 3 for the skinny FC GEMMs makes the
-// step 1 % faster (4.89 vs 4.94 ms) although fc6 forward alone goes from 410 to 556 us and its time becomes unstable; 3
-// for everything the same, 4 slower (5.21).  The default (2) is the setting that is best for the kernels on their own.
-#define g_split_target g_i2v_tuning[I2V_TUNE_SPLIT_TARGET]
-#define g_split_target_skinny g_i2v_tuning[I2V_TUNE_SPLIT_TARGET_SKINNY]
-#define g_split_below g_i2v_tuning[I2V_TUNE_SPLIT_BELOW]
-#define g_split_atomics g_i2v_tuning[I2V_TUNE_SPLIT_ATOMICS]
-#define g_big_fc_tile g_i2v_tuning[I2V_TUNE_BIG_FC_TILE]
-#define g_wgrad_v2 g_i2v_tuning[I2V_TUNE_WGRAD_V2]
-#define g_wgrad_fused_tile g_i2v_tuning[I2V_TUNE_WGRAD_FUSED_TILE]
-
-// Split-K workspace, provided by the CALLER (i2v_conv_split_workspace_bytes): [kSplitCounters arrival counters | slab of
-// partial tiles].  The counters must be zero before the first launch that uses the workspace; every launch leaves them
-// zero again (the last workgroup to arrive at a tile resets its counter).  Launches that share a workspace must be
-// ordered on the device (same stream, or graph edges): two concurrently running launches need two workspaces.
+// Tuning knobs live in g_i2v_tuning (i2v_set_tuning; the library itself reads no environment variable); conv_plan.h reads them.
 static int g_ordered_fallbacks = 0;      // i2v_ordered_fallbacks(): reductions asked to be ordered that ran on fp32 atomics
-constexpr int kSplitCounters = 1024;
-constexpr size_t kSplitCounterBytes = sizeof(int) * kSplitCounters;
 
-template <class K>
-void set_max_lds(K kernel) {
-    (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
+// One launch of a forward kernel that asks for up to 96 KB of dynamic LDS (allowed once per instantiation).
+template <auto Kernel>
+void launch_conv(dim3 grid, int threads, size_t lds, const ConvP& p, hipStream_t st) {
+    static const bool once = [] {
+        (void)hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
+        return true;
+    }();
+    (void)once;
+    Kernel<<<grid, threads, lds, st>>>(p);
 }
 
-constexpr int kKGroups = 4;      // wave groups of the intra-workgroup K split (16 waves = 4 per SIMD, one workgroup per CU)
+// the kernels of one tile shape, by form and mask
+template <int WAVES_M, int WAVES_N, int TM, int TN>
+void launch_tile(int form, const ConvP& p, hipStream_t st) {
+    constexpr int BM = WAVES_M * TM * 16, BN = WAVES_N * TN * 16;
+    const dim3 grid(i2v_cdiv(p.M, BM) * i2v_cdiv(p.N, BN), p.splitk, p.nbatch > 1 ? p.nbatch : 1);
+    const size_t lds_g = (size_t)(2 * (BM + BN) * BKS) * sizeof(float);
+    const bool mask = (p.flags & I2V_EPI_MASK) != 0;      // the MASK instantiations serve data gradients only
+    switch (form) {
+    case FORM_GEMM:
+        if (mask) launch_conv<conv_gemm_f32<WAVES_M, WAVES_N, TM, TN, false, true>>(grid, THREADS, lds_g, p, st);
+        else if (p.clk) launch_conv<conv_gemm_f32<WAVES_M, WAVES_N, TM, TN, true>>(grid, THREADS, lds_g, p, st);
+        else launch_conv<conv_gemm_f32<WAVES_M, WAVES_N, TM, TN>>(grid, THREADS, lds_g, p, st);
+        break;
+    case FORM_GEMM_DMA32:
+        if (mask) launch_conv<conv_gemm_f32<WAVES_M, WAVES_N, TM, TN, false, true, 1, 1>>(grid, THREADS, lds_g, p, st);
+        else launch_conv<conv_gemm_f32<WAVES_M, WAVES_N, TM, TN, false, false, 1, 1>>(grid, THREADS, lds_g, p, st);
+        break;
+    case FORM_GEMM_DMA16:
+        if (mask) launch_conv<conv_gemm_f32<WAVES_M, WAVES_N, TM, TN, false, true, 1, 2>>(grid, THREADS, lds_g / 2, p, st);
+        else launch_conv<conv_gemm_f32<WAVES_M, WAVES_N, TM, TN, false, false, 1, 2>>(grid, THREADS, lds_g / 2, p, st);
+        break;
+    default: {
+        const size_t stage = lds_g + p.ktab_entries * sizeof(float), epi = (size_t)BM * (BN + 4) * sizeof(float);
+        launch_conv<conv_igemm_f32<WAVES_M, WAVES_N, TM, TN>>(grid, THREADS, stage > epi ? stage : epi, p, st);
+    }
+    }
+}
 
 // The intra-workgroup K split (conv_gemm_f32<.., KG>): one workgroup of KG x 4 waves per tile, KG stage-buffer sets in LDS.
-// KG = 4 (round 4): 16 waves, 115-156 KB -- the workgroup owns its CU.  KG = 2 (round 5): 8 waves, 58-78 KB -- two of them, or
-// one and the 4-wave workgroups of the step's other branches, share a CU.
-template <int WAVES_M, int WAVES_N, int TM, int TN, int KG = kKGroups>
+template <int WAVES_M, int WAVES_N, int TM, int TN, int KG>
 int launch_kgroups(const ConvP& p, hipStream_t st) {
     constexpr int BM = WAVES_M * TM * 16, BN = WAVES_N * TN * 16;
     constexpr int need = KG * 2 * (BM + BN) * BKS * 4;
@@ -1110,221 +1122,68 @@ int launch_kgroups(const ConvP& p, hipStream_t st) {
     return I2V_OK;
 }
 
-template <int WAVES_M, int WAVES_N, int TM, int TN>
-void launch_tile(const ConvP& p, hipStream_t st) {
-    constexpr int BM = WAVES_M * TM * 16, BN = WAVES_N * TN * 16;
-    const int tiles = i2v_cdiv(p.M, BM) * i2v_cdiv(p.N, BN);
-    const size_t stage = (size_t)(2 * (BM + BN) * BKS + p.ktab_entries) * sizeof(float);
-    const size_t epi = (size_t)BM * (BN + 4) * sizeof(float);
-    const size_t lds = stage > epi ? stage : epi;
-    static bool once = [] {
-        set_max_lds(conv_igemm_f32<WAVES_M, WAVES_N, TM, TN>);
-        return true;
-    }();
-    (void)once;
-    const dim3 grid(tiles, p.splitk, p.nbatch > 1 ? p.nbatch : 1);
-    // pointwise layers / plain GEMMs whose split-K (if any) is finished in the kernel: the lean specialisation
-    const bool pointwise = p.KH == 1 && p.KW == 1 && p.pad == 0 && p.pad_x == 0 && p.stride == 1 && p.ostride == 1 &&
-                           p.Ho == p.H && p.Wo == p.W && (p.N & 3) == 0 && (p.K & 3) == 0 && (p.splitk <= 1 || p.ws);
-    if (pointwise && g_i2v_tuning[I2V_TUNE_CONV_GEMM]) {
-        static bool once_g = [] {
-            set_max_lds(conv_gemm_f32<WAVES_M, WAVES_N, TM, TN>);
-            set_max_lds(conv_gemm_f32<WAVES_M, WAVES_N, TM, TN, true>);
-            set_max_lds(conv_gemm_f32<WAVES_M, WAVES_N, TM, TN, false, true>);
-            set_max_lds(conv_gemm_f32<WAVES_M, WAVES_N, TM, TN, false, false, 1, 1>);
-            set_max_lds(conv_gemm_f32<WAVES_M, WAVES_N, TM, TN, false, true, 1, 1>);
-            return true;
-        }();
-        (void)once_g;
-        const size_t lds_g = (size_t)(2 * (BM + BN) * BKS) * sizeof(float);
-        // round 6: LDS-DMA staging (I2V_TUNE_GEMM_DMA: 1 = 32-k stages, 2 = 16-k stages / half the LDS; 0 = through registers)
-        const int dma = g_i2v_tuning[I2V_TUNE_GEMM_DMA];
-        if (dma > 0 && !p.clk) {
-            const bool mask = (p.flags & I2V_EPI_MASK) != 0;
-            if (dma == 2) {
-                if (mask) conv_gemm_f32<WAVES_M, WAVES_N, TM, TN, false, true, 1, 2><<<grid, THREADS, lds_g / 2, st>>>(p);
-                else conv_gemm_f32<WAVES_M, WAVES_N, TM, TN, false, false, 1, 2><<<grid, THREADS, lds_g / 2, st>>>(p);
-            } else {
-                if (mask) conv_gemm_f32<WAVES_M, WAVES_N, TM, TN, false, true, 1, 1><<<grid, THREADS, lds_g, st>>>(p);
-                else conv_gemm_f32<WAVES_M, WAVES_N, TM, TN, false, false, 1, 1><<<grid, THREADS, lds_g, st>>>(p);
-            }
-            return;
-        }
-        if (p.flags & I2V_EPI_MASK) conv_gemm_f32<WAVES_M, WAVES_N, TM, TN, false, true><<<grid, THREADS, lds_g, st>>>(p);
-        else if (p.clk) conv_gemm_f32<WAVES_M, WAVES_N, TM, TN, true><<<grid, THREADS, lds_g, st>>>(p);
-        else conv_gemm_f32<WAVES_M, WAVES_N, TM, TN><<<grid, THREADS, lds_g, st>>>(p);
-        return;
-    }
-    conv_igemm_f32<WAVES_M, WAVES_N, TM, TN><<<grid, THREADS, lds, st>>>(p);
+ConvShape shape_of(const ConvP& p) {
+    return {p.B, p.H, p.W, p.Cin, p.Cout, p.KH, p.KW, p.stride, p.pad, p.pad_x, p.ostride, p.Ho, p.Wo, p.nbatch, p.flags};
 }
 
-struct TileCfg { int bm, bn; float eff; };
-// eff: relative MFMA efficiency of the tile shape (operand reuse per LDS byte), from measurements
-constexpr TileCfg kTiles[] = {{128, 128, 1.00f}, {128, 64, 0.97f}, {96, 64, 0.95f}, {80, 64, 0.95f}, {64, 64, 0.93f},
-                              {32, 64, 0.80f}};
-constexpr int kNumTiles = sizeof(kTiles) / sizeof(kTiles[0]);
+// unsupported outcomes of a plan as the library's error
+int plan_error(int status, const ConvShape& s) {
+    if (status == PLAN_TAP_TABLE) i2v_set_error("conv: filter %dx%dx%d too large for the tap table", s.KH, s.KW, s.Cin);
+    else if (status == PLAN_OPERAND_2GIB) i2v_set_error("conv: operand larger than 2 GiB (32-bit buffer offsets)");
+    else if (status == PLAN_ROW_SCALE_NEEDS_V2) i2v_set_error("conv_wgrad_scaled: shape outside the v2 kernel (Cout % 4, 2 GiB operands)");
+    else if (status == PLAN_FUSED_NEEDS_SPLIT) i2v_set_error("conv_wgrad_sgd: shape needs a split over pixels; use i2v_conv_wgrad + i2v_sgd_momentum");
+    return status == PLAN_OK ? I2V_OK : I2V_ERR_UNSUPPORTED;
+}
 
+// plan (conv_plan.h), bind the workspace and clear, launch
 int run_conv(ConvP p, hipStream_t st, void* split_ws = nullptr, size_t split_ws_bytes = 0) {
+    const ConvShape shape = shape_of(p);
+    const FwdPlan pl = plan_conv_fwd(shape, g_i2v_tuning, g_force_tile, g_clk != nullptr, split_ws ? split_ws_bytes : 0);
+    if (pl.status != PLAN_OK) return plan_error(pl.status, shape);
     p.M = p.B * p.Ho * p.Wo;
     p.N = p.Cout;
     p.K = p.KH * p.KW * p.Cin;
     p.lgCin = ilog2_exact(p.Cin);
-    if (!(p.KH == 1 && p.KW == 1 && p.pad == 0 && p.pad_x == 0)) {
-        if (p.K > KTAB_MAX * 4 || p.KH * p.KW > 64 || ((long long)(p.KH * p.W + p.KW) * p.Cin) >= (1ll << 24)) {
-            i2v_set_error("conv: filter %dx%dx%d too large for the tap table", p.KH, p.KW, p.Cin);
-            return I2V_ERR_UNSUPPORTED;
-        }
-    }
-    p.ktab_entries = (p.KH == 1 && p.KW == 1 && p.pad == 0 && p.pad_x == 0) ? 4 : ((p.K + BKS - 1) / BKS) * (BKS / 4);
-    const long long xb = (long long)p.B * p.H * p.W * p.Cin * 4, wb = (long long)p.N * p.K * 4;
-    const long long halo = std::max(0ll, (long long)(p.pad * p.W + p.pad_x) * p.Cin * 4);    // the kernel's descriptor starts this much earlier
-    if (xb + halo >= (1ll << 31) || wb >= (1ll << 31)) {
-        i2v_set_error("conv: operand larger than 2 GiB (32-bit buffer offsets)");
-        return I2V_ERR_UNSUPPORTED;
-    }
-    p.x_bytes = (unsigned)xb;
-    p.w_bytes = (unsigned)wb;
+    p.ktab_entries = pl.ktab_entries;
+    p.x_bytes = pl.x_bytes;
+    p.w_bytes = pl.w_bytes;
     p.clk = g_clk;
     p.ablate = g_ablate;
-    const int force = p.force_tile;
-    const int ksteps = i2v_cdiv(p.K, BKS);
-    // tile + split-K choice: minimise (rounds over the 256 CUs) x (MACs per workgroup) / efficiency.
-    // The M of a 600x1000 frame pair at stride 16 is only 4788 rows, so wave quantisation decides
-    // the shape; skinny GEMMs (vrd FCs: M = 128 rows) fill the chip by splitting K.
-    auto plan = [&](int c, int& splitk) {
-        const long long t = (long long)i2v_cdiv(p.M, kTiles[c].bm) * i2v_cdiv(p.N, kTiles[c].bn) * (p.nbatch > 1 ? p.nbatch : 1);
-        splitk = 1;
-        if (t < g_split_below && ksteps >= 8 && p.ostride == 1 && p.nbatch <= 1) {
-            const int target = (p.M <= 256 && g_split_target_skinny > 0) ? g_split_target_skinny : g_split_target;
-            splitk = (int)((target * NUM_CU + t - 1) / t);
-            splitk = splitk > ksteps / 4 ? ksteps / 4 : splitk;
-            if (splitk < 1) splitk = 1;
-            // Under round 4's rule (SPLIT_ATOMICS == 2) a large output split more than kSplitInKernelMax ways leaves the in-kernel
-            // finish: fp32 atomics, a clear in front, a separate epilogue pass and the generic kernel -- none of which the 1.05
-            // below prices.  Found on 600x801 frames (round 6, tools/size_probe.py): layer3 conv1 of ONE frame (M = 1900) took
-            // 128x128 tiles x 8 splits = 240 workgroups, "one round", and ran at 42 TF on conv_igemm_f32 where the 64x64 x 4 plan
-            // runs at 80 on conv_gemm_f32 -- the loader-fed step was 7 % slower on the SMALLER frames.  Such outputs split at most
-            // kSplitInKernelMax ways.
-            if (g_split_atomics == 2 && splitk > kSplitInKernelMax && (long long)p.M * p.N >= (1 << 18)) splitk = kSplitInKernelMax;
-        }
-        const long long blocks = t * splitk;
-        const long long rounds = (blocks + NUM_CU - 1) / NUM_CU;
-        // beyond ~4 rounds several workgroups share a CU and the tail matters less
-        const double r = rounds <= 4 ? (double)rounds : (double)blocks / NUM_CU + 0.5;
-        double cost = r * kTiles[c].bm * kTiles[c].bn * (double)i2v_cdiv(ksteps, splitk) / kTiles[c].eff;
-        if (splitk > 1) cost *= 1.05;     // memset + atomics + separate epilogue pass
-        return cost;
-    };
-    int cfg = 0, splitk = 1;
-    double best = 1e300;
-    for (int c = 0; c < kNumTiles; ++c) {
-        int sk;
-        const double cost = plan(c, sk);
-        if (cost < best) { best = cost; cfg = c; splitk = sk; }
-    }
-    // HBM-bound pointwise layers (at most four K stages over many rows: the 64 -> 256 / 128 -> 512 expansions of layer1 / layer2 and
-    // their data gradients): the model's MAC count cannot tell the tiles apart (all within 2 %) and picks 128x64; measured, the
-    // 80x64 tile streams best (tools/pers_bench.py, two frames: layer1 conv3 44.0 against 50.7 us, layer2 conv3 33.3 against 37.6)
-    if (g_i2v_tuning[I2V_TUNE_STREAM_TILE] && p.KH == 1 && p.KW == 1 && p.stride == 1 && p.nbatch <= 1 && ksteps <= 4 && p.M >= 16384) {
-        cfg = 3;
-        plan(cfg, splitk);
-    }
-    // batched launches with at most four K stages (the Winograd planes of the 64- and 128-channel layers): per-workgroup
-    // set-up and epilogue dominate and the model underrates the smallest tile (measured 23.5 vs 27.4 us at 64 channels)
-    if (p.nbatch > 1 && ksteps <= 4) { cfg = kNumTiles - 1; plan(cfg, splitk); }
-    // the long skinny GEMM of the relation head (fc6 forward: 128 rows, K = 50176): 128x64 tiles instead of the 128x128 the
-    // model picks -- twice the workgroups, each half as heavy.  Alone 436 vs 412 us, inside the two-stream step 4.88 vs
-    // 4.93 ms (the same effect as with the fused update's tile: lighter workgroups give the other stream its turn sooner)
-    if (g_big_fc_tile >= 0 && g_big_fc_tile < kNumTiles && p.M <= 256 && p.K >= 16384) { cfg = g_big_fc_tile; plan(cfg, splitk); }
-    if (force >= 0 && force < kNumTiles) { cfg = force; plan(cfg, splitk); }
-    p.splitk = splitk;
-    p.k_per_split = i2v_cdiv(ksteps, splitk) * BKS;
-    p.splitk = i2v_cdiv(p.K, p.k_per_split);
-    // Intra-workgroup K split (conv_gemm_f32<.., KG>): a pointwise GEMM the plan would split over K through memory runs as ONE
-    // 16-wave workgroup per tile whose four wave groups each take a quarter of K and meet in LDS -- same waves per SIMD, no partial
-    // tile leaves the CU.  Its four stage-buffer sets leave room for one workgroup per CU, so it pays when the tiles of ONE round
-    // cover most of the chip: of the tiles 80x64 / 64x64 / 48x64 / 32x64 the smallest (least work per CU) with at most 256 tiles,
-    // if that is at least 180 (70 % of the CUs); otherwise the split across workgroups stays (layer3 conv1: 240 tiles of 80x64 for
-    // a frame pair, 200 of 48x64 for one frame; tools/kgroup_bench.py).  K a multiple of 4 x 32 with >= 2 stages per group.
-    int kg_tile = -1;
-    {
-        const bool pw = p.KH == 1 && p.KW == 1 && p.pad == 0 && p.pad_x == 0 && p.stride == 1 && p.ostride == 1 && p.Ho == p.H &&
-                        p.Wo == p.W && (p.N & 3) == 0 && (p.K & 3) == 0 && g_i2v_tuning[I2V_TUNE_CONV_GEMM];
-        const int kgn = g_i2v_tuning[I2V_TUNE_KGROUPS] == 2 ? 2 : kKGroups;       // wave groups: 2 (round 5), or 4 (1 / 4)
-        if (g_i2v_tuning[I2V_TUNE_KGROUPS] && pw && !p.clk && p.nbatch <= 1 && p.splitk >= 2 && force < 0 &&
-            p.K % (kgn * BKS) == 0 && p.K / kgn >= 2 * BKS &&
-            (long long)p.M * p.N >= (1 << 18)) {
-            static const int kg_bm[4] = {80, 64, 48, 32};
-            const int nt = i2v_cdiv(p.N, 64);
-            for (int c = 3; c >= 0; --c) {                       // smallest tile first
-                const int t = i2v_cdiv(p.M, kg_bm[c]) * nt;
-                if (t <= NUM_CU) { if (t >= (NUM_CU * 7) / 10) kg_tile = c; break; }
-            }
-            if (kg_tile >= 0) { p.splitk = 1; p.k_per_split = p.K; }
-        }
-    }
-    const long long ntiles = (long long)i2v_cdiv(p.M, kTiles[cfg].bm) * i2v_cdiv(p.N, kTiles[cfg].bn);
+    p.splitk = pl.splitk;
+    p.k_per_split = pl.k_per_split;
     p.ws = nullptr;
     p.cnt = nullptr;
-    const size_t ws_need = (size_t)p.splitk * ntiles * kTiles[cfg].bm * kTiles[cfg].bn * sizeof(float);
-    // in-kernel finish pays where the output is large (atomics and the extra epilogue pass scale with it);
-    // for the small FC outputs of the vrd head the atomics are cheap and a serial sum of many splits is not
-    // round 5: the ordered finish takes ANY number of splits (rounds of kSplitInKernelMax) and any output size, so that no
-    // forward or data-gradient GEMM of the relation head depends on arrival order (SPLIT_ATOMICS = 2 restores round 4's rule
-    // everywhere: atomics beyond four splits and for outputs under 2^18 elements; 1: atomics always)
-    // SPLIT_ATOMICS == 0 (what the relation step's head context selects, launch.LaunchContext(ordered=True)): ordered for every
-    // shape.  The process default is 2, round 4's rule: measured on configs[2], ordering every reduction of the step -- its
-    // 8-16-way filter-gradient splits, the bias sums of netD_style's 37500-row projections -- costs 46.2 -> 48.1 ms.
-    const bool r4_ok = p.splitk <= kSplitInKernelMax && (long long)p.M * p.N >= (1 << 18);
-    const bool wants_ws = p.splitk > 1 && g_split_atomics != 1 && (r4_ok || g_split_atomics == 0) &&
-                          ntiles <= kSplitCounters && ws_need < (1ull << 31) - (64u << 20);
-    // dry == 2: the workspace this shape would use (0: none)
-    if (p.dry == 2) return wants_ws ? (int)std::min<size_t>(kSplitCounterBytes + ws_need, 0x7FFFFFFF) : 0;
-    const bool in_kernel = wants_ws && split_ws && kSplitCounterBytes + ws_need <= split_ws_bytes;
-    // dry == 1: 0 = y needs no clear (no split, or the split is finished in-kernel), else the split factor
-    if (p.dry) return (p.splitk > 1 && !in_kernel) ? p.splitk : 0;
-    if (p.splitk > 1 && !in_kernel && g_split_atomics == 0) ++g_ordered_fallbacks;      // order was asked for; the workspace (or a size cap) refused
-    if (in_kernel) {
+    if (pl.finish == FIN_IN_KERNEL) {
         p.cnt = reinterpret_cast<int*>(split_ws);
         p.ws = reinterpret_cast<float*>(static_cast<char*>(split_ws) + kSplitCounterBytes);
     }
+    if (pl.ordered_fallback) ++g_ordered_fallbacks;
     const long long ytotal = (long long)p.M * p.N;
-    if (p.splitk > 1 && !p.ws && !(p.flags & I2V_EPI_ZEROED)) hipMemsetAsync(p.y, 0, (size_t)ytotal * sizeof(float), st);
-    if (kg_tile >= 0 && g_i2v_tuning[I2V_TUNE_KGROUPS] == 2) {
-        switch (kg_tile) {
-            case 0: return launch_kgroups<1, 4, 5, 1, 2>(p, st);
-            case 1: return launch_kgroups<2, 2, 2, 2, 2>(p, st);
-            case 2: return launch_kgroups<1, 4, 3, 1, 2>(p, st);
-            default: return launch_kgroups<2, 2, 1, 2, 2>(p, st);
-        }
+    if (pl.clear_y) hipMemsetAsync(p.y, 0, (size_t)ytotal * sizeof(float), st);
+    switch (pl.form == FORM_GEMM_KGROUPS2 ? 10 + pl.kg_tile : pl.form == FORM_GEMM_KGROUPS4 ? 20 + pl.kg_tile : pl.tile) {
+        case 0: launch_tile<2, 2, 4, 4>(pl.form, p, st); break;
+        case 1: launch_tile<2, 2, 4, 2>(pl.form, p, st); break;
+        case 2: launch_tile<2, 2, 3, 2>(pl.form, p, st); break;
+        case 3: launch_tile<1, 4, 5, 1>(pl.form, p, st); break;
+        case 4: launch_tile<2, 2, 2, 2>(pl.form, p, st); break;
+        case 5: launch_tile<2, 2, 1, 2>(pl.form, p, st); break;
+        case 10: return launch_kgroups<1, 4, 5, 1, 2>(p, st);
+        case 11: return launch_kgroups<2, 2, 2, 2, 2>(p, st);
+        case 12: return launch_kgroups<1, 4, 3, 1, 2>(p, st);
+        case 13: return launch_kgroups<2, 2, 1, 2, 2>(p, st);
+        case 20: return launch_kgroups<1, 4, 5, 1, kKGroups>(p, st);
+        case 21: return launch_kgroups<2, 2, 2, 2, kKGroups>(p, st);
+        case 22: return launch_kgroups<1, 4, 3, 1, kKGroups>(p, st);
+        case 23: return launch_kgroups<2, 2, 1, 2, kKGroups>(p, st);
     }
-    if (kg_tile >= 0) {
-        switch (kg_tile) {
-            case 0: return launch_kgroups<1, 4, 5, 1>(p, st);
-            case 1: return launch_kgroups<2, 2, 2, 2>(p, st);
-            case 2: return launch_kgroups<1, 4, 3, 1>(p, st);
-            default: return launch_kgroups<2, 2, 1, 2>(p, st);
-        }
-    }
-    switch (cfg) {
-        case 0: launch_tile<2, 2, 4, 4>(p, st); break;
-        case 1: launch_tile<2, 2, 4, 2>(p, st); break;
-        case 2: launch_tile<2, 2, 3, 2>(p, st); break;
-        case 3: launch_tile<1, 4, 5, 1>(p, st); break;
-        case 4: launch_tile<2, 2, 2, 2>(p, st); break;
-        default: launch_tile<2, 2, 1, 2>(p, st); break;
-    }
-    if (p.splitk > 1 && !p.ws && (p.flags & (I2V_EPI_SCALE | I2V_EPI_BIAS | I2V_EPI_RESIDUAL | I2V_EPI_RELU | I2V_EPI_MASK))) {
-        if (p.N % 4 == 0)
-            conv_epilogue_kernel<<<(int)fmin((double)i2v_cdiv(ytotal / 4, 256), 4096.0), 256, 0, st>>>(
-                p.y, p.scale, p.shift, p.res, p.mask, ytotal / 4, p.N, p.flags);
-        else
-            conv_epilogue_scalar_kernel<<<(int)fmin((double)i2v_cdiv(ytotal, 256), 4096.0), 256, 0, st>>>(
-                p.y, p.scale, p.shift, p.res, p.mask, ytotal, p.N, p.flags);
-    }
+    if (pl.epilogue_pass == PASS_VEC4)
+        conv_epilogue_kernel<<<(int)fmin((double)i2v_cdiv(ytotal / 4, 256), 4096.0), 256, 0, st>>>(
+            p.y, p.scale, p.shift, p.res, p.mask, ytotal / 4, p.N, p.flags);
+    else if (pl.epilogue_pass == PASS_SCALAR)
+        conv_epilogue_scalar_kernel<<<(int)fmin((double)i2v_cdiv(ytotal, 256), 4096.0), 256, 0, st>>>(
+            p.y, p.scale, p.shift, p.res, p.mask, ytotal, p.N, p.flags);
     return I2V_OK;
 }
-
 
 // ---------------------------------------------------------------- dgrad helper
 // wt[c][KH-1-ky][KW-1-kx][n] = w[n][ky][kx][c]: the filter of the transposed conv.
@@ -2493,14 +2352,9 @@ __global__ void __launch_bounds__(FCU_THREADS) fc_update_f32(const FcuP p) {    
 }
 }  // namespace
 
-// the persistent fused update (fc_update_f32); false: a shape it does not cover, which takes launch_wgrad's tiled kernel --
-// filters of more than one tap, more than 256 rows, Cout % 4 != 0 or the first-generation wgrad selected (their MFMA chain
-// differs: bit-equality holds against conv_wgrad2_f32 only), operands of 2 GiB or more
-static bool launch_fc_update(const WgP& p, hipStream_t st) {
-    if (!g_i2v_tuning[I2V_TUNE_FC_UPDATE] || !g_wgrad_v2) return false;
-    const bool lin = p.KH == 1 && p.KW == 1 && p.pad == 0 && p.stride == 1;
+// the persistent fused update (fc_update_f32), for the shapes plan_wgrad gives WG_FC_UPDATE
+static void launch_fc_update(const WgP& p, hipStream_t st) {
     const long long xb = (long long)p.M * p.K * 4, gb = (long long)p.M * p.N * 4, wb = (long long)p.N * p.K * 4;
-    if (!lin || p.M > 256 || p.N % 4 || p.K % 4 || xb >= (1ll << 31) || gb >= (1ll << 31) || wb >= (1ll << 31)) return false;
     FcuP q = {};
     q.x = p.x; q.gy = p.gy; q.w = p.gw; q.m = p.sgd_m; q.lr = p.lr; q.mom = p.mom; q.wd = p.wd;
     q.M = p.M; q.N = p.N; q.K = p.K;
@@ -2520,126 +2374,60 @@ static bool launch_fc_update(const WgP& p, hipStream_t st) {
     case 7: fc_update_f32<7><<<grid, FCU_THREADS, 0, st>>>(q); break;
     default: fc_update_f32<8><<<grid, FCU_THREADS, 0, st>>>(q); break;
     }
-    return true;
 }
 
-// picks the kernel + pixel split for one wgrad problem; returns false when v2 cannot be used
-constexpr int kWgradOrderedMax = 16;     // most splits the ordered finish of a filter gradient sums (one workgroup reads them all)
-
-// the pixel split launch_wgrad gives an unfused problem of `planes` x (N x K) filters over M reduction rows
-static int wgrad_split_count(long long M, int N, int K, int planes, int tm, int tk, int rs) {
-    const long long tiles = (long long)i2v_cdiv(N, tm) * i2v_cdiv(K, tk), all_tiles = tiles * planes;
-    const int msteps = i2v_cdiv(M, rs), per_cu = g_i2v_tuning[I2V_TUNE_WGRAD_PER_CU];
-    int splits = (int)((long long)per_cu * NUM_CU / all_tiles);
-    if (splits < 2) splits = (int)(((long long)per_cu * NUM_CU + all_tiles - 1) / all_tiles);
-    if (splits > msteps / 4) splits = msteps / 4;
-    if (splits < 1) splits = 1;
-    return splits;
+static ConvShape shape_of(const WgP& p) {
+    return {p.B, p.H, p.W, p.Cin, p.Cout, p.KH, p.KW, p.stride, p.pad, p.pad, 1, p.Ho, p.Wo, p.nbatch, 0};
 }
 
-// (csrc/winograd.hip) the parts a 36-plane Winograd filter gradient is split into when its sum is ordered: what its workspace holds
-int i2v_internal_wgrad_plane_splits(long long T, int Cout, int Cin) {
-    const int s = wgrad_split_count(T, Cout, Cin, 36, 64, 64, BKS);
-    const int mps = i2v_cdiv(i2v_cdiv(T, BKS), s) * BKS;
-    return i2v_cdiv(T, mps);
+// plan one filter-gradient problem (conv_plan.h); ext_part: p.part_ws is the caller's own slab of p.part_cap parts
+static WgradPlan plan_of(const WgP& p, float beta, bool fused, void* split_ws, size_t split_ws_bytes) {
+    return plan_wgrad(shape_of(p), beta != 0.f, fused, p.row_scale != nullptr, p.part_ws ? p.part_cap : -1, g_i2v_tuning,
+                      g_clk != nullptr, split_ws ? split_ws_bytes : 0);
 }
 
-static bool launch_wgrad(WgP& p, float beta, bool fused, hipStream_t st, void* split_ws = nullptr, size_t split_ws_bytes = 0) {
-    const long long xb = (long long)p.B * p.H * p.W * p.Cin * 4, gb = (long long)p.M * p.N * 4;
-    const bool v2 = (p.N % 4 == 0) && xb < (1ll << 31) && gb < (1ll << 31) && g_wgrad_v2;
-    if (p.row_scale && !v2) { i2v_set_error("conv_wgrad_scaled: shape outside the v2 kernel (Cout % 4, 2 GiB operands)"); return false; }
-    // bigger tiles raise the FLOP per staged byte (the reduction dim is streamed): 128x128 = 32 FLOP/B vs 16
-    int tm = 64, tk = 64;
-    // fused update: 128 filters x 64 taps -- the x tile is shared by twice the filters and half as many workgroups go
-    // through the dispatcher.  Alone the kernel is slower than the 64x64 form (fc6: 792 vs 736 us), inside the step it is
-    // faster (4.93 vs 5.00 ms, four alternating pairs): the rest of the step gets the chip back sooner
-    if (v2 && fused && g_wgrad_fused_tile == 128 && p.N >= 128) tm = 128;
-    if (v2 && g_wgrad_v2 >= 2) {
-        if (p.N >= 128) tm = 128;
-        if (p.K >= 128 && tm == 128 && g_wgrad_v2 == 2) tk = 128;
-    }
-    const long long tiles = (long long)i2v_cdiv(p.N, tm) * i2v_cdiv(p.K, tk);
-    const int rs = v2 ? BKS : 16;
-    int splits = 1;
-    const int msteps = i2v_cdiv(p.M, rs);
-    // one round of workgroups: floor, not ceil (144 tiles x 8 splits = 1152 workgroups on 1024 slots ran 1.5 rounds)
-    if (!fused) splits = wgrad_split_count(p.M, p.N, p.K, p.nbatch > 1 ? p.nbatch : 1, tm, tk, rs);
-    // Ordered finish (round 5; a caller that passes its split workspace): the split of a SMALL problem (under I2V_TUNE_WGRAD_ORDERED_GFLOP = 8 GFLOP: the
-    // relation head's conv_lo filters, its linear layers' data gradients), capped at kWgradOrderedMax parts, is summed in split
-    // order by the tile's last workgroup instead of with atomics -- bit-reproducible, and no clear of gw.  A large one (the
-    // instance_styleD backbone: up to 254 splits to fill the chip) keeps the atomics.
+// bind the workspace and clear, launch the planned kernel, then the reduce pass if the plan has one
+static void launch_wgrad(WgP& p, const WgradPlan& pl, float beta, hipStream_t st, void* split_ws = nullptr) {
+    if (pl.kernel == WG_FC_UPDATE) return launch_fc_update(p, st);
     const int planes = p.nbatch > 1 ? p.nbatch : 1;
-    // Round 6: every split a caller wants ordered IS ordered, whatever its size.  Up to kWgradOrderedMax parts of the
-    // second-generation kernel meet in the workspace as tiles and the tile's last workgroup sums them (round 5); more parts --
-    // the instance_styleD backbone splits up to 254 ways to fill the chip -- and the first-generation kernel (Cout % 4 != 0)
-    // store their partial FILTERS side by side and a reduce pass adds them in split order (part_ws; round 5 left these on
-    // atomics, and ran the first-generation kernel UNSPLIT when order was asked for: the RPN's 18-row cls_score gradient over
-    // 9576 pixels on eight workgroups, 300 us instead of 9 -- that alone was the "+4 %" ordered sums cost configs[2]).
-    const bool ext_part = p.part_ws != nullptr;       // the caller reduces (the Winograd filter gradient's final transform): its own slab
-    const double ord_flops = 1e9 * g_i2v_tuning[I2V_TUNE_WGRAD_ORDERED_GFLOP], flops = 2.0 * p.M * p.N * p.K * planes;
-    const bool want_ord = !fused && !ext_part && splits > 1 && g_i2v_tuning[I2V_TUNE_SPLIT_ATOMICS] == 0 && flops < ord_flops;
-    // a split beyond kWgradOrderedMax parts is capped where that costs nothing (under 1 GFLOP: conv_lo.0's 128-way split of a
-    // 0.3 GFLOP problem): the in-kernel finish needs no second launch
-    if (want_ord && split_ws && v2 && splits > kWgradOrderedMax && flops < 1e9) splits = kWgradOrderedMax;
-    if (ext_part && splits > p.part_cap) splits = p.part_cap > 0 ? p.part_cap : 1;
-    p.m_per_split = i2v_cdiv(msteps, splits) * rs;
-    splits = i2v_cdiv(p.M, p.m_per_split);
-    p.direct = (splits == 1 && beta == 0.f) || fused;
-    bool two_pass = false;
-    if (ext_part) {
-        if (splits == 1) p.part_ws = nullptr;         // one part: written straight to gw (the caller passed its slot 0 as gw)
-    } else if (want_ord && splits > 1) {
-        const size_t need_ord = kSplitCounterBytes + (size_t)splits * tiles * planes * (size_t)(tm * tk) * sizeof(float);
-        const size_t need_part = kSplitCounterBytes + (size_t)splits * planes * (size_t)p.N * p.K * sizeof(float);
-        if (split_ws && v2 && splits <= kWgradOrderedMax && tiles * planes <= kSplitCounters && need_ord <= split_ws_bytes && need_ord < (1ull << 31)) {
-            p.ord_cnt = reinterpret_cast<int*>(split_ws);
-            p.ord_ws = reinterpret_cast<float*>(static_cast<char*>(split_ws) + kSplitCounterBytes);
-            p.ord_splits = splits; p.ord_tiles = (int)tiles; p.ord_acc = beta != 0.f;
-        } else if (split_ws && need_part <= split_ws_bytes) {
-            p.part_ws = reinterpret_cast<float*>(static_cast<char*>(split_ws) + kSplitCounterBytes);      // the counters in front stay zero
-            two_pass = true;
-        } else {
-            ++g_ordered_fallbacks;                    // no workspace, or too small: fp32 atomics (i2v_ordered_fallbacks() tells)
-        }
+    p.m_per_split = pl.m_per_split;
+    p.direct = pl.direct;
+    p.x_bytes = pl.x_bytes;
+    p.gy_bytes = pl.gy_bytes;
+    if (pl.finish == WFIN_ORDERED_TILES) {
+        p.ord_cnt = reinterpret_cast<int*>(split_ws);
+        p.ord_ws = reinterpret_cast<float*>(static_cast<char*>(split_ws) + kSplitCounterBytes);
+        p.ord_splits = pl.splits; p.ord_tiles = pl.tiles; p.ord_acc = beta != 0.f;
+    } else if (pl.finish == WFIN_ORDERED_PARTS) {
+        p.part_ws = reinterpret_cast<float*>(static_cast<char*>(split_ws) + kSplitCounterBytes);      // the counters in front stay zero
+    } else if (pl.finish != WFIN_EXTERNAL_PARTS) {
+        p.part_ws = nullptr;                          // a caller's slab of one part: written straight to gw (its slot 0)
     }
-    if (beta == 0.f && !p.direct && !p.ord_ws && !p.part_ws)
-        hipMemsetAsync(p.gw, 0, (p.nbatch > 1 ? (size_t)(p.nbatch - 1) * p.bsw : 0) * sizeof(float) + (size_t)p.N * p.K * sizeof(float), st);
-    p.x_bytes = (unsigned)xb;
-    p.gy_bytes = (unsigned)gb;
-    dim3 grid((unsigned)tiles, splits, p.nbatch > 1 ? p.nbatch : 1);
-    const long long groups = (long long)splits * (p.nbatch > 1 ? p.nbatch : 1), total = tiles * groups;
-    // v2 kernels only (the remap lives there); one group needs no grouping; the 1-D launch must fit an int
-    p.xcd_remap = (v2 && groups >= 2 && total < (1ll << 30) && g_i2v_tuning[I2V_TUNE_WGRAD_XCD]) ? 1 : 0;
-    if (p.xcd_remap) {
-        p.r_tiles = (int)tiles; p.r_splits = splits; p.r_total = (int)total;
-        grid = dim3((unsigned)((total + 7) / 8 * 8), 1, 1);
+    if (pl.ordered_fallback) ++g_ordered_fallbacks;
+    if (pl.clear_bytes) hipMemsetAsync(p.gw, 0, pl.clear_bytes, st);
+    p.xcd_remap = pl.xcd_remap;
+    if (pl.xcd_remap) { p.r_tiles = pl.tiles; p.r_splits = pl.splits; p.r_total = pl.tiles * pl.splits * planes; }
+    const dim3 grid(pl.grid[0], pl.grid[1], pl.grid[2]);
+    switch (pl.kernel) {
+    case WG_V1_64x64: conv_wgrad_f32<64, 64><<<grid, THREADS, 0, st>>>(p); break;
+    case WG_V2_DMA_128x128: conv_wgrad2_f32<4, 4, false, false, true><<<grid, THREADS, 0, st>>>(p); break;
+    case WG_V2_DMA_128x64: conv_wgrad2_f32<4, 2, false, false, true><<<grid, THREADS, 0, st>>>(p); break;
+    case WG_V2_DMA_64x64: conv_wgrad2_f32<2, 2, false, false, true><<<grid, THREADS, 0, st>>>(p); break;
+    case WG_V2_FUSED_128x64: conv_wgrad2_f32<4, 2, true><<<grid, THREADS, 0, st>>>(p); break;
+    case WG_V2_128x128: conv_wgrad2_f32<4, 4><<<grid, THREADS, 0, st>>>(p); break;
+    case WG_V2_128x64: conv_wgrad2_f32<4, 2><<<grid, THREADS, 0, st>>>(p); break;
+    case WG_V2_FUSED_64x64: conv_wgrad2_f32<2, 2, true><<<grid, THREADS, 0, st>>>(p); break;
+    case WG_V2_CLK_64x64: p.clk = g_clk; p.abl = g_ablate; conv_wgrad2_f32<2, 2, false, true><<<grid, THREADS, 0, st>>>(p); break;
+    default: conv_wgrad2_f32<2, 2><<<grid, THREADS, 0, st>>>(p); break;
     }
-    // round 6: LDS-DMA staging for the pointwise / linear problems (most of a backbone's filter-gradient time: the 1x1 layers and
-    // the Winograd-domain plane GEMMs)
-    const bool lin = p.KH == 1 && p.KW == 1 && p.pad == 0 && p.stride == 1;
-    const bool dma = v2 && !fused && !g_clk && lin && (p.K % 4 == 0) && g_i2v_tuning[I2V_TUNE_WGRAD_DMA];
-    if (!v2) conv_wgrad_f32<64, 64><<<grid, THREADS, 0, st>>>(p);
-    else if (dma && tm == 128 && tk == 128) conv_wgrad2_f32<4, 4, false, false, true><<<grid, THREADS, 0, st>>>(p);
-    else if (dma && tm == 128) conv_wgrad2_f32<4, 2, false, false, true><<<grid, THREADS, 0, st>>>(p);
-    else if (dma) conv_wgrad2_f32<2, 2, false, false, true><<<grid, THREADS, 0, st>>>(p);
-    else if (fused && tm == 128 && tk == 64) conv_wgrad2_f32<4, 2, true><<<grid, THREADS, 0, st>>>(p);
-    else if (tm == 128 && tk == 128) conv_wgrad2_f32<4, 4><<<grid, THREADS, 0, st>>>(p);
-    else if (tm == 128) conv_wgrad2_f32<4, 2><<<grid, THREADS, 0, st>>>(p);
-    else if (fused) conv_wgrad2_f32<2, 2, true><<<grid, THREADS, 0, st>>>(p);
-    else if (g_clk) { p.clk = g_clk; p.abl = g_ablate; conv_wgrad2_f32<2, 2, false, true><<<grid, THREADS, 0, st>>>(p); }
-    else conv_wgrad2_f32<2, 2><<<grid, THREADS, 0, st>>>(p);
-    if (ext_part) p.ord_splits = splits;              // what the caller's reduce pass must sum
-    if (two_pass) {
-        const long long nk = (long long)p.N * p.K;
-        if ((nk & 3) == 0) {
-            const long long total = (long long)planes * (nk / 4);
-            wgrad_reduce_kernel<<<(unsigned)std::min<long long>(i2v_cdiv(total, 256), 2048), 256, 0, st>>>(
-                p.part_ws, p.gw, splits, planes, nk / 4, planes > 1 ? p.bsw : nk, beta != 0.f);
-        } else {
-            wgrad_reduce_scalar_kernel<<<(unsigned)std::min<long long>(i2v_cdiv(nk, 256), 2048), 256, 0, st>>>(p.part_ws, p.gw, splits, nk, beta != 0.f);
-        }
+    const long long nk = (long long)p.N * p.K;
+    if (pl.reduce_pass == PASS_VEC4) {
+        const long long total = (long long)planes * (nk / 4);
+        wgrad_reduce_kernel<<<(unsigned)std::min<long long>(i2v_cdiv(total, 256), 2048), 256, 0, st>>>(
+            p.part_ws, p.gw, pl.splits, planes, nk / 4, planes > 1 ? p.bsw : nk, beta != 0.f);
+    } else if (pl.reduce_pass == PASS_SCALAR) {
+        wgrad_reduce_scalar_kernel<<<(unsigned)std::min<long long>(i2v_cdiv(nk, 256), 2048), 256, 0, st>>>(p.part_ws, p.gw, pl.splits, nk, beta != 0.f);
     }
-    return true;
 }
 
 static int check_conv(const char* who, const void* a, const void* b, const void* c, int B, int H, int W, int Cin,
@@ -2680,17 +2468,16 @@ extern "C" int32_t i2v_conv_set_tile(int32_t cfg) {
     return I2V_OK;
 }
 
-static int plan_conv(int dry, size_t ws_bytes, int32_t B, int32_t H, int32_t W, int32_t Cin, int32_t Cout, int32_t KH,
-                     int32_t KW, int32_t stride, int32_t pad) {
+// the plan of i2v_conv_fwd (nbatch <= 1) or i2v_gemm_nt_batched (its M x K operand as a 1 x M x 1 x K activation) for a shape
+static int plan_conv(const char* who, FwdPlan& pl, size_t ws_bytes, int32_t B, int32_t H, int32_t W, int32_t Cin, int32_t Cout,
+                     int32_t KH, int32_t KW, int32_t stride, int32_t pad, int32_t nbatch = 0, int32_t flags = 0) {
     int dummy = 0;
-    int rc = check_conv("conv_fwd_splits", &dummy, &dummy, &dummy, B, H, W, Cin, Cout, KH, KW, stride, pad);
+    int rc = check_conv(who, &dummy, &dummy, &dummy, B, H, W, Cin, Cout, KH, KW, stride, pad);
     if (rc) return rc;
-    ConvP p = {};
-    p.B = B; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout; p.KH = KH; p.KW = KW; p.stride = stride; p.pad = pad; p.pad_x = pad;
-    p.Ho = (H + 2 * pad - KH) / stride + 1;
-    p.Wo = (W + 2 * pad - KW) / stride + 1;
-    p.ostride = 1; p.force_tile = g_force_tile; p.dry = dry;
-    return run_conv(p, nullptr, ws_bytes ? &dummy : nullptr, ws_bytes);
+    const ConvShape s = {B, H, W, Cin, Cout, KH, KW, stride, pad, pad, 1, (H + 2 * pad - KH) / stride + 1, (W + 2 * pad - KW) / stride + 1,
+                         nbatch, flags};
+    pl = plan_conv_fwd(s, g_i2v_tuning, g_force_tile, g_clk != nullptr, ws_bytes);
+    return plan_error(pl.status, s);
 }
 
 // 1 if i2v_conv_fwd, given a split-K workspace of ws_bytes, will accumulate split-K partials with atomics for this
@@ -2698,16 +2485,53 @@ static int plan_conv(int dry, size_t ws_bytes, int32_t B, int32_t H, int32_t W, 
 // 0 otherwise, < 0 on error.
 extern "C" int32_t i2v_conv_fwd_splits(int32_t B, int32_t H, int32_t W, int32_t Cin, int32_t Cout, int32_t KH,
                                        int32_t KW, int32_t stride, int32_t pad, size_t ws_bytes) {
-    const int rc = plan_conv(1, ws_bytes, B, H, W, Cin, Cout, KH, KW, stride, pad);
-    return rc < 0 ? rc : (rc > 1 ? 1 : 0);
+    FwdPlan pl = {};
+    const int rc = plan_conv("conv_fwd_splits", pl, ws_bytes, B, H, W, Cin, Cout, KH, KW, stride, pad);
+    return rc < 0 ? rc : pl.finish == FIN_ATOMICS;
 }
 
 // Bytes of split-K workspace i2v_conv_fwd would use for this shape (0: it does not split K, or it splits into so many
 // parts / so small an output that fp32 atomics are the better finish).
 extern "C" size_t i2v_conv_split_workspace_bytes(int32_t B, int32_t H, int32_t W, int32_t Cin, int32_t Cout, int32_t KH,
                                                  int32_t KW, int32_t stride, int32_t pad) {
-    const int rc = plan_conv(2, 0, B, H, W, Cin, Cout, KH, KW, stride, pad);
-    return rc > 0 ? (size_t)rc : 0;
+    FwdPlan pl = {};
+    return plan_conv("conv_fwd_splits", pl, 0, B, H, W, Cin, Cout, KH, KW, stride, pad) ? 0 : pl.ws_wanted;
+}
+
+static int32_t clamp32(size_t v) { return (int32_t)std::min<size_t>(v, 0x7FFFFFFF); }
+
+// The forward plan as numbers (include/i2vsgg_hip.h has the field order): what the launch of this shape would do.
+extern "C" int32_t i2v_conv_fwd_plan(int32_t B, int32_t H, int32_t W, int32_t Cin, int32_t Cout, int32_t KH, int32_t KW,
+                                     int32_t stride, int32_t pad, int32_t nbatch, int32_t flags, size_t ws_bytes, int32_t* out,
+                                     int32_t n_out) {
+    I2V_CHECK_ARG(out && n_out >= I2V_FWD_PLAN_FIELDS, "conv_fwd_plan: out needs room for I2V_FWD_PLAN_FIELDS values");
+    FwdPlan pl = {};
+    const int rc = plan_conv("conv_fwd_plan", pl, ws_bytes, B, H, W, Cin, Cout, KH, KW, stride, pad, nbatch, flags);
+    if (rc && pl.status == PLAN_OK) return rc;      // a bad argument; an unsupported shape is reported in out[0]
+    const int32_t v[I2V_FWD_PLAN_FIELDS] = {pl.status, pl.tile, pl.splitk, pl.k_per_split, pl.ktab_entries, pl.form, pl.kg_tile,
+                                            pl.finish, clamp32(pl.ws_wanted), clamp32(pl.ws_used), pl.clear_y, pl.epilogue_pass,
+                                            pl.ordered_fallback};
+    std::copy(v, v + I2V_FWD_PLAN_FIELDS, out);
+    return I2V_OK;
+}
+
+// The filter-gradient plan as numbers: i2v_conv_wgrad / _scaled (fused = 0), i2v_conv_wgrad_sgd (fused = 1), or, with
+// nbatch > 1, the plane batch of i2v_gemm_tn_batched (B = H = 1, W = M, Cin = K, Cout = N, 1x1).
+extern "C" int32_t i2v_conv_wgrad_plan(int32_t B, int32_t H, int32_t W, int32_t Cin, int32_t Cout, int32_t KH, int32_t KW,
+                                       int32_t stride, int32_t pad, int32_t nbatch, int32_t beta_nonzero, int32_t fused,
+                                       int32_t has_row_scale, int32_t ext_part_cap, size_t ws_bytes, int32_t* out, int32_t n_out) {
+    I2V_CHECK_ARG(out && n_out >= I2V_WGRAD_PLAN_FIELDS, "conv_wgrad_plan: out needs room for I2V_WGRAD_PLAN_FIELDS values");
+    int dummy = 0;
+    const int rc = check_conv("conv_wgrad_plan", &dummy, &dummy, &dummy, B, H, W, Cin, Cout, KH, KW, stride, pad);
+    if (rc) return rc;
+    const ConvShape s = {B, H, W, Cin, Cout, KH, KW, stride, pad, pad, 1, (H + 2 * pad - KH) / stride + 1, (W + 2 * pad - KW) / stride + 1,
+                         nbatch, 0};
+    const WgradPlan pl = plan_wgrad(s, beta_nonzero != 0, fused != 0, has_row_scale != 0, ext_part_cap, g_i2v_tuning, g_clk != nullptr, ws_bytes);
+    const int32_t v[I2V_WGRAD_PLAN_FIELDS] = {pl.status, pl.v2, pl.kernel, pl.tm, pl.tk, pl.splits, pl.m_per_split, pl.finish, pl.direct,
+                                              pl.xcd_remap, (int32_t)pl.grid[0], (int32_t)pl.grid[1], (int32_t)pl.grid[2], pl.dma,
+                                              clamp32(pl.clear_bytes), pl.reduce_pass, pl.ordered_fallback};
+    std::copy(v, v + I2V_WGRAD_PLAN_FIELDS, out);
+    return I2V_OK;
 }
 
 extern "C" int32_t i2v_conv_fwd(const float* x, const float* w, const float* scale, const float* shift,
@@ -2725,7 +2549,6 @@ extern "C" int32_t i2v_conv_fwd(const float* x, const float* w, const float* sca
     p.Ho = (H + 2 * pad - KH) / stride + 1;
     p.Wo = (W + 2 * pad - KW) / stride + 1;
     p.flags = flags; p.ostride = 1; p.Hy = p.Ho; p.Wy = p.Wo;
-    p.force_tile = g_force_tile;
     rc = run_conv(p, (hipStream_t)stream, split_ws, split_ws_bytes);
     if (rc) return rc;
     I2V_CHECK_LAUNCH("conv_fwd");
@@ -2743,7 +2566,6 @@ extern "C" int32_t i2v_gemm_nt_batched(const float* a, const float* b, float* c,
     p.x = a; p.w = b; p.y = c;
     p.B = 1; p.H = M; p.W = 1; p.Cin = K; p.Cout = N; p.KH = 1; p.KW = 1; p.stride = 1; p.pad = 0; p.pad_x = 0;
     p.Ho = M; p.Wo = 1; p.flags = 0; p.ostride = 1; p.Hy = M; p.Wy = 1;
-    p.force_tile = g_force_tile;
     p.nbatch = nbatch; p.bsx = stride_a; p.bsw = stride_b; p.bsy = stride_c;
     int rc = run_conv(p, (hipStream_t)stream, split_ws, split_ws_bytes);
     if (rc) return rc;
@@ -2793,7 +2615,6 @@ static int conv_dgrad_impl(const float* gy, const float* w, const float* gy_scal
     if (out_scale) { p.scale = out_scale; p.shift = nullptr; p.flags |= I2V_EPI_SCALE; }
     if (res) { p.res = res; p.flags |= I2V_EPI_RESIDUAL; }
     if (mask) { p.mask = mask; p.flags |= I2V_EPI_MASK; }
-    p.force_tile = g_force_tile;
     p.Hy = H; p.Wy = W;
     const bool pointwise = KH == 1 && KW == 1 && pad == 0;
     if (stride == 1 || pointwise) {
@@ -2879,7 +2700,9 @@ static int conv_wgrad_impl(const float* x, const float* gy, float* gw, const flo
     p.M = B * p.Ho * p.Wo; p.N = Cout; p.K = KH * KW * Cin;
     p.lgCin = ilog2_exact(Cin);
     I2V_CHECK_ARG(beta == 0.f || beta == 1.f, "conv_wgrad: beta must be 0 or 1");
-    if (!launch_wgrad(p, beta, false, st, split_ws, split_ws_bytes)) return I2V_ERR_UNSUPPORTED;
+    const WgradPlan pl = plan_of(p, beta, false, split_ws, split_ws_bytes);
+    if (pl.status != PLAN_OK) return plan_error(pl.status, shape_of(p));
+    launch_wgrad(p, pl, beta, st, split_ws);
     I2V_CHECK_LAUNCH("conv_wgrad");
     return I2V_OK;
 }
@@ -2901,15 +2724,16 @@ static int32_t gemm_tn_batched_impl(const float* x, const float* gy, float* gw, 
     p.M = M; p.N = N; p.K = K;
     p.lgCin = ilog2_exact(K);
     p.nbatch = nbatch; p.bsx = stride_x; p.bsg = stride_gy; p.bsw = stride_gw;
-    if (!g_wgrad_v2 || (long long)M * K * 4 >= (1ll << 31) || (long long)M * N * 4 >= (1ll << 31)) {
-        i2v_set_error("gemm_tn_batched: operand larger than 2 GiB per batch");
-        return I2V_ERR_UNSUPPORTED;
-    }
     if (part_splits) {          // i2v_internal_gemm_tn_batched_parts: gw = a slab of part_cap slots of nbatch x (N x K); slot s = split s
         p.part_ws = gw; p.part_cap = part_cap;
     }
-    launch_wgrad(p, beta, false, (hipStream_t)stream);
-    if (part_splits) *part_splits = p.part_ws ? p.ord_splits : 1;
+    const WgradPlan pl = plan_of(p, beta, false, nullptr, 0);
+    if (!pl.v2) {               // N % 4 == 0 was checked: the first-generation kernel is selected, or an operand reaches 2 GiB
+        i2v_set_error("gemm_tn_batched: operand larger than 2 GiB per batch");
+        return I2V_ERR_UNSUPPORTED;
+    }
+    launch_wgrad(p, pl, beta, (hipStream_t)stream);
+    if (part_splits) *part_splits = pl.splits;      // what the caller's reduce pass must sum (1: the result itself)
     I2V_CHECK_LAUNCH("gemm_tn_batched");
     return I2V_OK;
 }
@@ -2973,12 +2797,9 @@ extern "C" int32_t i2v_conv_wgrad_sgd(const float* x, const float* gy, float* w,
     p.Wo = (W + 2 * pad - KW) / stride + 1;
     p.M = B * p.Ho * p.Wo; p.N = Cout; p.K = KH * KW * Cin;
     p.lgCin = ilog2_exact(Cin);
-    const long long tiles = (long long)i2v_cdiv(p.N, 64) * i2v_cdiv(p.K, 64);
-    if (tiles < 2 * NUM_CU || p.M > 4096) {
-        i2v_set_error("conv_wgrad_sgd: shape needs a split over pixels; use i2v_conv_wgrad + i2v_sgd_momentum");
-        return I2V_ERR_UNSUPPORTED;
-    }
-    if (!launch_fc_update(p, (hipStream_t)stream)) launch_wgrad(p, 0.f, true, (hipStream_t)stream);
+    const WgradPlan pl = plan_of(p, 0.f, true, nullptr, 0);      // the persistent update, or a shape it does not cover on the tiled kernel
+    if (pl.status != PLAN_OK) return plan_error(pl.status, shape_of(p));
+    launch_wgrad(p, pl, 0.f, (hipStream_t)stream);
     I2V_CHECK_LAUNCH("conv_wgrad_sgd");
     return I2V_OK;
 }

@@ -11,6 +11,7 @@
 // xi = 4*row + col of the 4x4 transform domain.  Only the GEMM uses the matrix cores; the two transforms are
 // streaming kernels that overlap with MFMA work of the other stream.
 #include "common.h"
+#include "conv_plan.h"
 #include <algorithm>
 
 extern "C" int32_t i2v_gemm_tn_batched(const float* x, const float* gy, float* gw, int32_t M, int32_t N, int32_t K,
@@ -655,7 +656,7 @@ extern "C" size_t i2v_conv3x3_winograd4_wgrad_workspace_bytes(int32_t B, int32_t
     const size_t T = (size_t)B * ((H + 3) / 4) * ((W + 3) / 4);
     // the last region holds the 36 plane gradients -- once per part of the pixel split, so that an ordered sum
     // (I2V_TUNE_SPLIT_ATOMICS == 0) can leave the parts side by side for the final transform to add in order
-    const size_t parts = (size_t)i2v_internal_wgrad_plane_splits((long long)T, Cout, Cin);
+    const size_t parts = (size_t)convplan::wgrad_plane_splits((long long)T, Cout, Cin, g_i2v_tuning);
     return i2v_align(36 * T * Cin * sizeof(float)) + i2v_align(36 * T * Cout * sizeof(float)) +
            i2v_align(36 * (size_t)Cout * Cin * sizeof(float) * (parts > 1 ? parts : 1));
 }

@@ -12,6 +12,8 @@ Conventions
   * no CPU fallback: non-CUDA tensors raise.
 """
 
+import ctypes
+
 import numpy as np
 import torch
 
@@ -367,13 +369,13 @@ def _conv_fwd_raw(x, w, scale, shift, res, stride, pad, flags, out=None):
             flags |= EPI_ZEROED
     if y is None:
         y = torch.empty((B, Cout, Ho, Wo), device=x.device, dtype=torch.float32, memory_format=_CL)
-    # which kernel serves the call (profiling only): pointwise layers whose split-K, if any, finishes in the kernel run on
-    # conv_gemm_f32, everything else on conv_igemm_f32 (csrc/conv.hip, launch_tile)
+    # which kernel serves the call (profiling only): the plan's form (include/i2vsgg_hip.h, i2v_conv_fwd_plan) -- 0 is
+    # conv_igemm_f32, every other one a form of conv_gemm_f32
     kern = ""
     if PROFILE is not None:
-        pointwise = (KH, KW, stride, pad) == (1, 1, 1, 0) and Cout % 4 == 0 and Cin % 4 == 0
-        kern = " [gemm]" if pointwise and lib.i2v_get_tuning(10) and \
-            lib.i2v_conv_fwd_splits(B, H, W, Cin, Cout, KH, KW, stride, pad, sws.numel()) == 0 else " [igemm]"
+        plan = (ctypes.c_int32 * 13)()
+        check(lib.i2v_conv_fwd_plan(B, H, W, Cin, Cout, KH, KW, stride, pad, 0, flags, sws.numel(), plan, 13), "conv_fwd_plan")
+        kern = " [gemm]" if plan[0] == 0 and plan[5] != 0 else " [igemm]"
     with _Timed(2.0 * B * Ho * Wo * Cout * KH * KW * Cin, "fwd",
                 "M%d N%d K%d (%dx%d s%d)%s" % (B * Ho * Wo, Cout, KH * KW * Cin, KH, KW, stride, kern),
                 4 * (x.numel() + w.numel() + y.numel() + (res.numel() if res is not None else 0))):

@@ -316,6 +316,42 @@ int32_t i2v_conv_fwd_splits(int32_t B, int32_t H, int32_t W, int32_t Cin, int32_
                             int32_t stride, int32_t pad, size_t ws_bytes);
 size_t  i2v_conv_split_workspace_bytes(int32_t B, int32_t H, int32_t W, int32_t Cin, int32_t Cout, int32_t KH,
                                        int32_t KW, int32_t stride, int32_t pad);
+/* The launch plans, for diagnosis and tests (csrc/conv_plan.h computes them; the launches follow them).  Pure functions of
+ * the shape, the tuning table, i2v_conv_set_tile and the workspace size offered: nothing is launched, nothing counted.
+ * Each writes its fields as int32 into out[0 .. n_out) (n_out >= I2V_*_PLAN_FIELDS) and returns 0, or < 0 for a bad
+ * argument; a shape the kernels do not take is a plan with out[0] != 0.  Byte counts saturate at 2^31 - 1.
+ * i2v_conv_fwd_plan: i2v_conv_fwd's launch of the shape with `flags`, or, with nbatch > 1, i2v_gemm_nt_batched's (B = 1,
+ * H = M, W = 1, Cin = K, Cout = N, 1x1).  Fields:
+ *    0 status        0 ok, 1 filter too large for the tap table, 2 operand of 2 GiB or more
+ *    1 tile          0..5: 128x128, 128x64, 96x64, 80x64, 64x64, 32x64 outputs per workgroup
+ *    2 splitk        3 k_per_split        4 ktab_entries (tap-table entries in LDS)
+ *    5 form          0 IGEMM (conv_igemm_f32), 1 GEMM (conv_gemm_f32), 2 GEMM_DMA32, 3 GEMM_DMA16 (LDS-DMA staging, 32- / 16-k
+ *                    stages), 4 GEMM_KGROUPS2, 5 GEMM_KGROUPS4 (K split over 2 / 4 wave groups of one workgroup)
+ *    6 kg_tile       K-group forms: 0..3 = 80x64, 64x64, 48x64, 32x64; else -1
+ *    7 finish        0 NONE (K not split across workgroups), 1 IN_KERNEL (ordered, through the workspace), 2 ATOMICS
+ *    8 ws_wanted     workspace bytes the shape would use        9 ws_used  what it uses of ws_bytes (0: too small)
+ *   10 clear_y       the launch clears y first       11 epilogue_pass  0 none, 1 float4 pass, 2 scalar pass after the atomics
+ *   12 ordered_fallback  order was asked for (I2V_TUNE_SPLIT_ATOMICS == 0) and refused: i2v_ordered_fallbacks() would count it
+ * i2v_conv_wgrad_plan: i2v_conv_wgrad / _scaled (fused = 0), i2v_conv_wgrad_sgd (fused = 1), or, with nbatch > 1, the plane
+ * batch of i2v_gemm_tn_batched (B = H = 1, W = M, Cin = K, Cout = N, 1x1).  ext_part_cap >= 0: the caller sums the parts
+ * itself and has room for that many (the Winograd filter gradient); -1: none.  Fields:
+ *    0 status        0 ok, 3 row_scale needs the second-generation kernel, 4 a fused update would need a split over pixels
+ *    1 v2            the second-generation kernel serves the shape
+ *    2 kernel        0 v1 64x64; v2: 1 DMA 128x128, 2 DMA 128x64, 3 DMA 64x64, 4 fused 128x64, 5 128x128, 6 128x64, 7 fused
+ *                    64x64, 8 clocked 64x64, 9 64x64; 10 the persistent fused update (fields 3.. are 0 then, but 5 and 8)
+ *    3 tm  4 tk      filters x taps per workgroup       5 splits  6 m_per_split  (parts of the pixel reduction)
+ *    7 finish        0 DIRECT, 1 ATOMICS, 2 ORDERED_TILES (in the kernel, through the workspace), 3 ORDERED_PARTS (partial
+ *                    filters + reduce pass), 4 EXTERNAL_PARTS (the caller's slab)
+ *    8 direct        the kernel stores instead of adding        9 xcd_remap        10..12 grid x, y, z
+ *   13 dma           LDS-DMA staging      14 clear_bytes (gw cleared first)      15 reduce_pass  0 none, 1 float4, 2 scalar
+ *   16 ordered_fallback */
+#define I2V_FWD_PLAN_FIELDS   13
+#define I2V_WGRAD_PLAN_FIELDS 17
+int32_t i2v_conv_fwd_plan(int32_t B, int32_t H, int32_t W, int32_t Cin, int32_t Cout, int32_t KH, int32_t KW,
+                          int32_t stride, int32_t pad, int32_t nbatch, int32_t flags, size_t ws_bytes, int32_t* out, int32_t n_out);
+int32_t i2v_conv_wgrad_plan(int32_t B, int32_t H, int32_t W, int32_t Cin, int32_t Cout, int32_t KH, int32_t KW,
+                            int32_t stride, int32_t pad, int32_t nbatch, int32_t beta_nonzero, int32_t fused,
+                            int32_t has_row_scale, int32_t ext_part_cap, size_t ws_bytes, int32_t* out, int32_t n_out);
 /* Tuning knobs (process-wide, host side only; the library reads no environment variable).  key = I2V_TUNE_*. */
 #define I2V_TUNE_CONV_SPEC            0   /* retired (rounds 1-5: the 8-wave loader / MFMA specialisation of conv_igemm_f32): only <= 0 is accepted */
 #define I2V_TUNE_SPLIT_TARGET         1   /* workgroups per CU a split-K launch aims for (default 2) */

@@ -1579,3 +1579,109 @@ def test_fused_adam_equals_torch_adam():
 def cfg_double_bias():
     from i2vsgg_amd.model.utils.config import cfg
     return bool(cfg.TRAIN.DOUBLE_BIAS)
+
+
+def _smallest_rows(rows, key, floor=1 << 20):
+    """Per value of key(row): the row with the fewest MACs, but at least ``floor`` of them where the table has such a row (the
+    tests' degenerate shapes -- one filter, five rows -- say little about a tile)."""
+    best = {}
+    for r in rows:
+        B, H, W, Cin, Cout, KH, KW = r["args"][:7]
+        macs = B * H * W * Cin * Cout * KH * KW * max(r["args"][9], 1)
+        k, rank = key(r), (macs < floor, macs)
+        if k not in best or rank < best[k][0]:
+            best[k] = (rank, r)
+    return {k: v[1] for k, v in best.items()}
+
+
+def test_every_planned_form_and_finish_runs_once(ops):
+    """One launch per kernel form x finish of the forward GEMM plan and per finish (and kernel generation) of the filter-gradient
+    plan (csrc/conv_plan.h): for each, the smallest problem of tests/golden/conv_plans.json -- shapes the steps and the tests
+    above already run -- that the plan export says takes it, under the tuning its row names, through ``ops`` with the default
+    context's split workspace, against float64 torch.  Operands are scaled so that outputs are O(1).  Unordered finishes:
+    rtol = atol = 2e-5.  Ordered ones (the in-kernel split-K finish, the K-group forms, ordered tiles / parts): 2e-6 of the output
+    scale, and two launches give the same bits.  The caller-summed parts exist only inside the Winograd filter gradient, whose
+    F(4x4,3x3) transforms (entries up to 8 and down to 1/24, in fp32 on both sides of the plane GEMMs) set its error, not the GEMM:
+    it is held to its neighbour's bound (test_winograd_filter_gradient_vs_torch: 2e-4 of the scale) against float64, to the same
+    bits over two launches, and to 2e-5 of the scale against the same transforms with the planes summed by atomics."""
+    import json
+    from test_conv_plan_host import FWD_FINISHES, FWD_FORMS, TABLE, WGRAD_FINISHES, plan_of, tuned
+    from i2vsgg_amd import launch
+    from i2vsgg_amd._lib import lib, ptr, stream
+    WS = launch.SplitWorkspace.BYTES
+    with open(TABLE) as f:
+        rows = [r for r in json.load(f)["rows"] if r["plan"][0] == 0]
+    cl = lambda t: t.contiguous(memory_format=torch.channels_last)
+    gen = torch.Generator(device=DEV).manual_seed(3)
+    randn = lambda *s: torch.randn(*s, device=DEV, generator=gen)
+    ordered_fwd = lambda form, fin: fin == FWD_FINISHES["IN_KERNEL"] or form in (FWD_FORMS["GEMM_KGROUPS2"], FWD_FORMS["GEMM_KGROUPS4"])
+
+    # ---- forward: conv + frozen-BN scale/shift + ReLU
+    fwd = _smallest_rows([r for r in rows if r["kind"] == "fwd" and r["args"][9] <= 1 and r["args"][11] == WS],
+                         lambda r: (r["plan"][5], r["plan"][7]))
+    seen_fwd = set()
+    for (form, fin), row in sorted(fwd.items()):
+        B, H, W, Cin, Cout, KH, KW, stride, pad = row["args"][:9]
+        x, w = cl(randn(B, Cin, H, W)), cl(randn(Cout, Cin, KH, KW) / float(np.sqrt(KH * KW * Cin)))
+        sc, sh = torch.rand(Cout, device=DEV, generator=gen) + 0.5, torch.rand(Cout, device=DEV, generator=gen) - 0.5
+        with tuned(lib, row):
+            now = plan_of(lib, dict(row, args=row["args"][:9] + [0, 0, launch.split_buffer(torch.device(DEV)).numel()]))
+            assert (now[5], now[7]) == (form, fin), (row, now)
+            y = ops.conv2d(x, w, sc, sh, None, stride, pad, relu=True).clone()
+            again = ops.conv2d(x, w, sc, sh, None, stride, pad, relu=True) if ordered_fwd(form, fin) else None
+        ref = torch.relu(F.conv2d(x.double(), w.double(), None, stride, pad) * sc.double().view(1, -1, 1, 1) + sh.double().view(1, -1, 1, 1))
+        err, scale = float((y.double() - ref).abs().max()), float(ref.abs().max())
+        record_margin("test_every_planned_form_and_finish_runs_once", "fwd form %d finish %d %r" % (form, fin, row["args"][:9]), err / scale,
+                      2e-6 if again is not None else 2e-5)
+        if again is not None:
+            assert torch.equal(again, y), row
+            assert err <= 2e-6 * scale, (row, err, scale)
+        else:
+            np.testing.assert_allclose(y.cpu().numpy(), ref.float().cpu().numpy(), rtol=2e-5, atol=2e-5)
+        seen_fwd.add((form, fin))
+    # a plane batch (the element-wise planes of a Winograd layer): one launch of nbatch independent GEMMs
+    planes = _smallest_rows([r for r in rows if r["kind"] == "fwd" and r["args"][9] > 1 and r["args"][11] == 0], lambda r: 0)[0]
+    M, K, N, nb = planes["args"][1], planes["args"][3], planes["args"][4], planes["args"][9]
+    a, b, c = randn(nb, M, K), randn(nb, N, K) / float(np.sqrt(K)), torch.empty((nb, M, N), device=DEV)
+    with tuned(lib, planes):
+        assert plan_of(lib, planes) == planes["plan"]
+        assert lib.i2v_gemm_nt_batched(ptr(a), ptr(b), ptr(c), M, N, K, nb, M * K, N * K, M * N, None, 0, stream()) == 0
+    np.testing.assert_allclose(c.cpu().numpy(), torch.bmm(a.double(), b.double().transpose(1, 2)).float().cpu().numpy(), rtol=2e-5, atol=2e-5)
+    seen_fwd.add((planes["plan"][5], planes["plan"][7]))
+    assert {f for f, _ in seen_fwd} == set(FWD_FORMS.values()) and {f for _, f in seen_fwd} == set(FWD_FINISHES.values()), seen_fwd
+
+    # ---- filter gradients (beta = 0, no row scale): per finish and kernel generation
+    wg = _smallest_rows([r for r in rows if r["kind"] == "wgrad" and r["args"][10:13] == [0, 0, 0] and
+                         ((r["args"][9] <= 1 and r["args"][14] == WS) or r["plan"][7] == WGRAD_FINISHES["EXTERNAL_PARTS"])],
+                        lambda r: (r["plan"][7], r["plan"][1]))
+    seen_wg = set()
+    for (fin, v2), row in sorted(wg.items()):
+        B, H, W, Cin, Cout, KH, KW, stride, pad = row["args"][:9]
+        ext = fin == WGRAD_FINISHES["EXTERNAL_PARTS"]
+        if ext:                      # T tiles of 4x4 pixels in one row of tiles; the 3x3 layer whose planes the row describes
+            B, H, W, KH, KW, pad = 1, 4, 4 * row["args"][2], 3, 3, 1
+        Ho, Wo = (H + 2 * pad - KH) // stride + 1, (W + 2 * pad - KW) // stride + 1
+        x, g = cl(randn(B, Cin, H, W)), cl(randn(B, Cout, Ho, Wo) / float(np.sqrt(B * Ho * Wo)))
+        ordered = fin in (WGRAD_FINISHES["ORDERED_TILES"], WGRAD_FINISHES["ORDERED_PARTS"], WGRAD_FINISHES["EXTERNAL_PARTS"])
+        with tuned(lib, row):
+            assert plan_of(lib, row) == row["plan"]
+            gw = ops._conv_wgrad_raw(x, g, (Cout, Cin, KH, KW), stride, pad, winograd=ext).clone()
+            again = ops._conv_wgrad_raw(x, g, (Cout, Cin, KH, KW), stride, pad, winograd=ext) if ordered else None
+        ref = torch.nn.grad.conv2d_weight(x.double(), (Cout, Cin, KH, KW), g.double(), stride, pad)
+        err, scale = float((gw.double() - ref).abs().max()), float(ref.abs().max())
+        bound = 2e-4 if ext else 2e-6 if ordered else 2e-5
+        record_margin("test_every_planned_form_and_finish_runs_once", "wgrad finish %d v2 %d %r" % (fin, v2, row["args"][:10]), err / scale, bound)
+        if ordered:
+            assert torch.equal(again, gw), row
+            assert err <= bound * scale, (row, err, scale)
+        else:
+            np.testing.assert_allclose(gw.cpu().numpy(), ref.float().cpu().numpy(), rtol=2e-5, atol=2e-5)
+        if ext:                      # the same transforms, the planes' parts summed by atomics (the default context's call form)
+            assert lib.i2v_get_tuning(4) == 2
+            plain = ops._conv_wgrad_raw(x, g, (Cout, Cin, KH, KW), stride, pad, winograd=True)
+            diff = float((plain - gw).abs().max())
+            record_margin("test_every_planned_form_and_finish_runs_once", "wgrad external parts vs atomics", diff / scale, 2e-5)
+            assert diff <= 2e-5 * scale, (row, diff, scale)
+        seen_wg.add(fin)
+    assert seen_wg == set(WGRAD_FINISHES.values()), seen_wg
+    assert {v2 for _, v2 in wg} == {0, 1}              # both kernel generations ran (Cout % 4 != 0 takes the first)
