@@ -9,6 +9,8 @@ Conventions
   * every function launches on torch's current stream and never synchronises;
   * scratch, the split-K workspace and pre-zeroed outputs come from the current ``launch.LaunchContext`` (``launch.py``
     owns them, the role streams and the graph branches; nothing here decides which buffer a launch may touch);
+  * which kernel family serves a conv layer's forward, data gradient and filter gradient is ``conv_route.plan_conv``'s decision,
+    asked once per layer; the wrappers here execute the route they are handed;
   * no CPU fallback: non-CUDA tensors raise.
 """
 
@@ -17,9 +19,9 @@ import ctypes
 import numpy as np
 import torch
 
-from . import _lib, launch
-from ._lib import (EPI_BIAS, EPI_RELU, EPI_RESIDUAL, EPI_SCALE, EPI_ZEROED, LAYOUT_NCHW, LAYOUT_NHWC, check, lib, ptr,
-                   stream)
+from . import _lib, conv_route, launch
+from ._lib import EPI_RELU, EPI_RESIDUAL, EPI_SCALE, EPI_ZEROED, LAYOUT_NCHW, LAYOUT_NHWC, check, lib, ptr, stream
+from .conv_route import ARENA, AS_WGRAD, DIRECT, WINOGRAD, WINOGRAD_V
 
 _CL = torch.channels_last
 
@@ -345,7 +347,36 @@ def param_key(w):
     return (w.data_ptr(), w._version, w.device, PARAM_EPOCH if getattr(w, "_i2v_trained", False) else 0)
 
 
-SMALL_GW_BYTES = 16 << 20
+# ---- the switches of the kernel routes (conv_route.py decides with them; tests and layers.py assign them here)
+SMALL_GW_BYTES = 16 << 20     # filter gradients up to this size may accumulate into the step's pre-zeroed arena
+LINEAR_DGRAD_AS_WGRAD = 0     # filter elements from which a linear layer's dgrad goes through the wgrad kernel
+# I2V_WINOGRAD_TRAIN=0: direct kernels for trained 3x3 layers too (fp32 error 1e-6 instead of 1e-5 per layer)
+WINOGRAD_TRAIN = True
+WINOGRAD_TRAIN_MIN_C = 64
+# I2V_WINOGRAD_WGRAD=0: the filter gradient of a trained 3x3 layer stays on the direct kernel (its forward and data gradient
+# are Winograd F(4x4,3x3) with WINOGRAD_TRAIN)
+WINOGRAD_WGRAD = True
+# I2V_WINOGRAD_KEEP_V=0: a trained 3x3 layer transforms its input again for the filter gradient instead of keeping the forward's
+# transformed input (36/16 of the activation's size per layer, ~1.9 GB over the 33 layers of an 8-frame instance_styleD step)
+WINOGRAD_KEEP_V = True
+# I2V_BLOCK_FUSED=0: every conv of a trained bottleneck is its own autograd node again (one streaming pass over the
+# activation gradient per conv for the BN scale / ReLU mask, the skip connection's gradient added by autograd)
+BLOCK_FUSED = True
+
+
+def _switches():
+    return conv_route.Switches(WINOGRAD_TRAIN, WINOGRAD_WGRAD, WINOGRAD_KEEP_V, WINOGRAD_TRAIN_MIN_C, LINEAR_DGRAD_AS_WGRAD,
+                               SMALL_GW_BYTES)
+
+
+def _plan(in_shape, w_shape, stride, pad, **layer):
+    """conv_route.plan_conv under the switches as they stand now."""
+    return conv_route.plan_conv(tuple(in_shape), tuple(w_shape), stride, pad, _switches(), **layer)
+
+
+def _wgrad_route(w_shape, stride, pad):
+    """The filter-gradient route of a layer that is asked for nothing else (tests, tools): Winograd from x where eligible."""
+    return _plan((1, w_shape[1], 1, 1), w_shape, stride, pad, needs_w=True).wgrad
 
 
 def _conv_fwd_raw(x, w, scale, shift, res, stride, pad, flags, out=None):
@@ -387,77 +418,72 @@ def _conv_fwd_raw(x, w, scale, shift, res, stride, pad, flags, out=None):
     return y
 
 
-LINEAR_DGRAD_AS_WGRAD = 0     # filter elements from which a linear layer's dgrad goes through the wgrad kernel
-
-
-def _linear_dgrad_as_wgrad(in_shape, w_shape, stride, pad):
-    B, Cin, H, W = in_shape
-    Cout, _, KH, KW = w_shape
-    return (H, W, KH, KW, stride, pad) == (1, 1, 1, 1, 1, 0) and B <= Cin and (Cout * Cin >= LINEAR_DGRAD_AS_WGRAD or Cout % 4 != 0)
-
-
-def _conv_dgrad_raw(g, w, in_shape, stride, pad):
+def _dgrad(g, w, in_shape, stride, pad, epilogue=None):
+    """The direct data gradient.  ``epilogue`` None: gx = dgrad(g, w) (i2v_conv_dgrad).  Else (gy_scale, out_scale, res, mask),
+    each a tensor or None: gx = mask > 0 ? (dgrad(g * gy_scale, w) * out_scale + res) : 0 of a stride-1 layer or a strided 1x1
+    layer (gx is then zero off the stride grid, and so must ``res`` be) (i2v_conv_dgrad_fused)."""
     B, Cin, H, W = in_shape
     Cout, _, KH, KW = w.shape
     dev = g.device
-    if _linear_dgrad_as_wgrad(in_shape, w.shape, stride, pad):
-        # linear layer: gx[m][k] = sum_n g[m][n] w[n][k] is a 'filter gradient' whose pixel axis is n, whose activations
-        # are w as stored (n x k) and whose output gradient is g^T (n x m) -- only the small g is transposed, where the
-        # implicit-GEMM form re-lays the whole filter out first (fc7: 134 -> 48 us in the step, the 64-row layers
-        # 14-20 -> 10 us; Cout % 4 != 0: no zero-padded copies).  Only while g is the smaller of the two (rows <= in-features):
-        # netD_style's 37500-row projections keep the implicit-GEMM form
-        gt = g.reshape(B, Cout).t().contiguous().view(Cout, B, 1, 1)
-        return _conv_wgrad_raw(w, gt, (B, Cin, 1, 1), 1, 0, tag="dgrad")
-    if Cout % 4:
-        # the transposed conv reduces over Cout: pad it to a float4 boundary with zero filters
-        padc = 4 - Cout % 4
-        g = torch.nn.functional.pad(g, (0, 0, 0, 0, 0, padc)).contiguous(memory_format=_CL)
-        w = torch.cat([w, w.new_zeros((padc,) + tuple(w.shape[1:]))], 0).contiguous(memory_format=_CL)
-        Cout += padc
     gx = torch.empty((B, Cin, H, W), device=dev, dtype=torch.float32, memory_format=_CL)
     ws = launch.workspace(lib.i2v_conv_dgrad_workspace_bytes(Cin, Cout, KH, KW), dev, "dgrad")
     sws = launch.split_buffer(dev)
+    extra = sum(t.numel() for t in epilogue[2:] if t is not None) if epilogue is not None else 0
     with _Timed(2.0 * B * g.shape[2] * g.shape[3] * Cout * KH * KW * Cin, "dgrad",
-                "M%d N%d K%d" % (B * H * W, Cin, KH * KW * Cout), 4 * (g.numel() + w.numel() + gx.numel())):
-        check(lib.i2v_conv_dgrad(ptr(g), ptr(w), ptr(gx), B, H, W, Cin, Cout, KH, KW, stride, pad, ptr(ws), ws.numel(),
-                                 ptr(sws), sws.numel(), stream()), "conv_dgrad")
+                "M%d N%d K%d" % (B * H * W, Cin, KH * KW * Cout) + (" +epi" if epilogue is not None else ""),
+                4 * (g.numel() + w.numel() + gx.numel() + extra)):
+        if epilogue is None:
+            check(lib.i2v_conv_dgrad(ptr(g), ptr(w), ptr(gx), B, H, W, Cin, Cout, KH, KW, stride, pad, ptr(ws), ws.numel(),
+                                     ptr(sws), sws.numel(), stream()), "conv_dgrad")
+        else:
+            check(lib.i2v_conv_dgrad_fused(ptr(g), ptr(w), *[ptr(t) for t in epilogue], ptr(gx), B, H, W, Cin, Cout, KH, KW,
+                                           stride, pad, ptr(ws), ws.numel(), ptr(sws), sws.numel(), stream()), "conv_dgrad_fused")
     return gx
 
 
-# I2V_WINOGRAD_WGRAD=0: the filter gradient of a trained 3x3 layer stays on the direct kernel (its forward and data gradient
-# are Winograd F(4x4,3x3) with WINOGRAD_TRAIN)
-WINOGRAD_WGRAD = True
+def _conv_dgrad_raw(g, w, in_shape, stride, pad, route=None, g_t=None):
+    """Data gradient on the implicit-GEMM kernels.  ``route``: (AS_WGRAD | DIRECT, dgrad_pad) of the layer's plan; None: a
+    gradient that is no layer of its own (netD_style's projections) is planned here.  ``g_t``: g transposed, when the
+    backward's epilogue pass has already written it."""
+    B, Cin, H, W = in_shape
+    Cout = w.shape[0]
+    how, padc = route if route is not None else conv_route.plan_dgrad(tuple(in_shape), tuple(w.shape), stride, pad, _switches())
+    if how == AS_WGRAD:
+        # only the small g is transposed (conv_route.plan_dgrad has the why)
+        if g_t is None:
+            g_t = g.reshape(B, Cout).t().contiguous().view(Cout, B, 1, 1)
+        return _conv_wgrad_raw(w, g_t, (B, Cin, 1, 1), 1, 0, tag="dgrad")
+    if padc:
+        # the transposed conv reduces over Cout: pad it to a float4 boundary with zero filters
+        g = torch.nn.functional.pad(g, (0, 0, 0, 0, 0, padc)).contiguous(memory_format=_CL)
+        w = torch.cat([w, w.new_zeros((padc,) + tuple(w.shape[1:]))], 0).contiguous(memory_format=_CL)
+    return _dgrad(g, w, in_shape, stride, pad)
 
 
-def _winograd_wgrad_ok(x, w_shape, stride, pad):
-    Cout, Cin, KH, KW = w_shape
-    return (WINOGRAD_WGRAD and WINOGRAD_TRAIN and (KH, KW, stride, pad) == (3, 3, 1, 1) and Cin % 4 == 0 and Cout % 4 == 0
-            and Cin >= WINOGRAD_TRAIN_MIN_C and Cout >= WINOGRAD_TRAIN_MIN_C)
+def _dgrad_fused(g, w, in_shape, pad, gy_scale=None, out_scale=None, res=None, mask=None, stride=1):
+    """``_dgrad`` with the epilogue of a block's backward."""
+    return _dgrad(g, w, in_shape, stride, pad, (gy_scale, out_scale, res, mask))
 
 
-def _conv_wgrad_raw(x, g, w_shape, stride, pad, tag="wgrad", row_scale=None, winograd=False, v=None):
+def _conv_wgrad_raw(x, g, w_shape, stride, pad, tag="wgrad", row_scale=None, route=DIRECT, v=None):
+    """Filter gradient by ``route`` (a conv_route wgrad value; WINOGRAD_V reads ``v``, the forward's transformed input)."""
     B, Cin, H, W = x.shape
     Cout, _, KH, KW = w_shape
-    # small filters: the pixel reduction is split over workgroups and accumulated with atomics, which needs a
-    # zeroed gw -- take it from the step's pre-zeroed arena and accumulate (beta = 1) instead of one clear per call
     gw, beta = None, 0.0
     n = Cout * Cin * KH * KW
-    # up to 224 pixels the launcher never splits the reduction (fewer than 8 stages of 32): one workgroup per tile
-    # stores its result directly -- no zeroed output, no atomics
     arena = launch.arena()
-    if arena is not None and n * 4 <= SMALL_GW_BYTES and B * g.shape[2] * g.shape[3] > 224:
+    if conv_route.wgrad_placement(n, B * g.shape[2] * g.shape[3], arena is not None, _switches()) == ARENA:
         flat = arena.take_flat(n)
         if flat is not None:
             gw, beta = flat.view(Cout, KH, KW, Cin).permute(0, 3, 1, 2), 1.0
     if gw is None:
         gw = torch.empty(w_shape, device=x.device, dtype=torch.float32, memory_format=_CL)
-    if winograd and _winograd_wgrad_ok(x, w_shape, stride, pad):
+    if route != DIRECT:
         # stride-1 / pad-1 3x3 layer of a trained bottleneck: 36 plane GEMMs over the 4x4 tiles, a quarter of the MACs
         ws = launch.workspace(lib.i2v_conv3x3_winograd4_wgrad_workspace_bytes(B, H, W, Cin, Cout), x.device, "winograd_wgrad")
-        T = B * ((H + 3) // 4) * ((W + 3) // 4)
         with _Timed(2.0 * B * H * W * Cout * 9 * Cin, tag, "N%d K%d M%d (3x3 winograd F4)" % (Cout, 9 * Cin, B * H * W),
                     4 * (x.numel() + g.numel() + gw.numel())):
-            if v is not None:       # the forward's transformed input
+            if route == WINOGRAD_V:
                 check(lib.i2v_conv3x3_winograd4_wgrad_v(ptr(v), ptr(g), ptr(row_scale), ptr(gw), B, H, W, Cin, Cout, beta, ptr(ws),
                                                         ws.numel(), stream()), "conv3x3_winograd4_wgrad_v")
             else:
@@ -505,11 +531,6 @@ def _conv_wgrad_sgd_raw(x, g, w, cfg, stride, pad):
     return rc
 
 
-# I2V_WINOGRAD_TRAIN=0: direct kernels for trained 3x3 layers too (fp32 error 1e-6 instead of 1e-5 per layer)
-WINOGRAD_TRAIN = True
-WINOGRAD_TRAIN_MIN_C = 64
-
-
 class _ConvFn(torch.autograd.Function):
     """y = relu?( conv(x,w)*scale + shift + res ).  scale/shift of a frozen BN get no gradient;
     a bias (shift without scale) does."""
@@ -519,35 +540,18 @@ class _ConvFn(torch.autograd.Function):
         _need_cuda(x, w)
         x = as_nhwc(x)
         w = as_nhwc(w)
-        flags = 0
-        if scale is not None:
-            flags |= EPI_SCALE
-        elif shift is not None:
-            flags |= EPI_BIAS
         if res is not None:
             res = as_nhwc(res)
-            flags |= EPI_RESIDUAL
-        if relu:
-            flags |= EPI_RELU
-        # a trained stride-1 / pad-1 3x3 layer whose caller allows it (the bottleneck 3x3s: instance_styleD trains
-        # layer1-3 and layer4): forward and data gradient as Winograd F(4x4,3x3) with the filter transformed each step
-        # (it changes each step); wgrad stays direct.  Not the RPN's 3x3: proposal ranking between near-tied scores
-        # follows the conv's last bits, and the direct kernel's 1e-6 keeps 99 % of the reference's proposals, 1e-5 97 %
-        wino = (wino_ok and WINOGRAD_TRAIN and (ctx.needs_input_grad[0] or ctx.needs_input_grad[1]) and res is None and stride == 1
-                and pad == 1 and tuple(w.shape[2:]) == (3, 3)
-                and w.shape[1] >= WINOGRAD_TRAIN_MIN_C and w.shape[0] >= WINOGRAD_TRAIN_MIN_C and w.shape[1] % 4 == 0)
+        need = ctx.needs_input_grad
+        route = _plan(x.shape, w.shape, stride, pad, scale=scale is not None, shift=shift is not None, res=res is not None,
+                      relu=relu, winograd_ok=wino_ok, needs_x=need[0], needs_w=need[1],
+                      needs_bias=need[3] and shift is not None and scale is None)
         v = None
-        if wino:
-            keep = WINOGRAD_KEEP_V and ctx.needs_input_grad[1] and _winograd_wgrad_ok(x, w.shape, stride, pad)
-            y, v = conv3x3_winograd(x, winograd_filter(w.detach(), 4), scale, shift, relu, keep_v=keep) if keep else \
-                (conv3x3_winograd(x, winograd_filter(w.detach(), 4), scale, shift, relu), None)
+        if route.fwd == WINOGRAD:
+            y, v = _winograd_fwd(x, winograd_filter(w.detach(), 4), scale, shift, relu, keep_v=route.keep_v)
         else:
-            y = _conv_fwd_raw(x, w, scale, shift, res, stride, pad, flags)
-        ctx.wino = wino
-        # the data gradient of an eligible 3x3 layer takes the Winograd form even where the forward may not (the RPN conv)
-        ctx.wino_dgrad = wino or (WINOGRAD_TRAIN and WINOGRAD_WGRAD and stride == 1 and pad == 1 and tuple(w.shape[2:]) == (3, 3)
-                                  and w.shape[1] >= WINOGRAD_TRAIN_MIN_C and w.shape[0] >= WINOGRAD_TRAIN_MIN_C
-                                  and w.shape[1] % 4 == 0 and w.shape[0] % 4 == 0)
+            y = _conv_fwd_raw(x, w, scale, shift, res, stride, pad, route.flags)
+        ctx.route = route
         ctx.cfg = (stride, pad, relu, scale is not None, shift is not None, res is not None)
         ctx.save_for_backward(x, w, scale, y if relu else None, v)
         return y
@@ -556,6 +560,7 @@ class _ConvFn(torch.autograd.Function):
     def backward(ctx, gy):
         x, w, scale, y, v = ctx.saved_tensors
         stride, pad, relu, has_scale, has_shift, has_res = ctx.cfg
+        route = ctx.route
         gy = as_nhwc(gy)
         M, N = gy.shape[0] * gy.shape[2] * gy.shape[3], gy.shape[1]
         gres = g_t = None
@@ -577,7 +582,7 @@ class _ConvFn(torch.autograd.Function):
             gpre = torch.empty_like(gy) if (want_pre and has_scale) else None
             # a linear layer whose data gradient will run on the wgrad kernel wants g column-major as well: written by
             # this pass instead of a transpose kernel of its own
-            if ctx.needs_input_grad[0] and not ctx.wino_dgrad and _linear_dgrad_as_wgrad(x.shape, w.shape, stride, pad):
+            if route.transposed_g:
                 g_t = torch.empty((N, M, 1, 1), device=gy.device, dtype=torch.float32)
             check(lib.i2v_epilogue_bwd(ptr(gy), ptr(y), ptr(scale) if has_scale else None, ptr(g), ptr(gpre), ptr(gbias),
                                        M, N, int(relu), ptr(g_t), *launch.split_args(), stream()), "epilogue_bwd")
@@ -590,51 +595,20 @@ class _ConvFn(torch.autograd.Function):
             gres = gy if need_res else None
         gx = None
         if ctx.needs_input_grad[0]:
-            if ctx.wino_dgrad:
-                gx = conv3x3_winograd(g, winograd_filter_dgrad(w), tag="dgrad")
-            elif g_t is not None:
-                gx = _conv_wgrad_raw(w, g_t, (x.shape[0], x.shape[1], 1, 1), 1, 0, tag="dgrad")
+            if route.dgrad == WINOGRAD:
+                gx, _ = _winograd_fwd(g, winograd_filter_dgrad(w), tag="dgrad")
             else:
-                gx = _conv_dgrad_raw(g, w, x.shape, stride, pad)
+                gx = _conv_dgrad_raw(g, w, x.shape, stride, pad, (route.dgrad, route.dgrad_pad), g_t)
         gw = None
         if ctx.needs_input_grad[1]:
             fused = FUSED_SGD.get(w.data_ptr())
             # the filter is read by dgrad above before it is updated here
             if fused is None or _conv_wgrad_sgd_raw(x, g, w, fused, stride, pad) != 0:
-                # Winograd filter gradient for every eligible 3x3 (the RPN's too: its FORWARD stays direct for the proposal
-                # ranking's sake, the filter gradient only feeds the next step's weights)
-                gw = _conv_wgrad_raw(x, g, w.shape, stride, pad, winograd=True, v=v)
+                gw = _conv_wgrad_raw(x, g, w.shape, stride, pad, route=route.wgrad, v=v)
         return gx, gw, None, gbias, gres, None, None, None, None
 
 
 # ---------------------------------------------------------------- a trained bottleneck as ONE autograd node
-# I2V_BLOCK_FUSED=0: every conv of a trained bottleneck is its own autograd node again (one streaming pass over the
-# activation gradient per conv for the BN scale / ReLU mask, the skip connection's gradient added by autograd)
-BLOCK_FUSED = True
-
-
-def _dgrad_fused(g, w, in_shape, pad, gy_scale=None, out_scale=None, res=None, mask=None, stride=1):
-    """gx = mask > 0 ? (dgrad(g * gy_scale, w) * out_scale + res) : 0 of a stride-1 layer or a strided 1x1 layer (gx is then
-    zero off the stride grid, and so must ``res`` be) (i2v_conv_dgrad_fused)."""
-    B, Cin, H, W = in_shape
-    Cout, _, KH, KW = w.shape
-    gx = torch.empty((B, Cin, H, W), device=g.device, dtype=torch.float32, memory_format=_CL)
-    ws = launch.workspace(lib.i2v_conv_dgrad_workspace_bytes(Cin, Cout, KH, KW), g.device, "dgrad")
-    sws = launch.split_buffer(g.device)
-    extra = (res.numel() if res is not None else 0) + (mask.numel() if mask is not None else 0)
-    with _Timed(2.0 * B * g.shape[2] * g.shape[3] * Cout * KH * KW * Cin, "dgrad", "M%d N%d K%d +epi" % (B * H * W, Cin, KH * KW * Cout),
-                4 * (g.numel() + w.numel() + gx.numel() + extra)):
-        check(lib.i2v_conv_dgrad_fused(ptr(g), ptr(w), ptr(gy_scale), ptr(out_scale), ptr(res), ptr(mask), ptr(gx), B, H, W,
-                                       Cin, Cout, KH, KW, stride, pad, ptr(ws), ws.numel(), ptr(sws), sws.numel(), stream()),
-              "conv_dgrad_fused")
-    return gx
-
-
-def _wgrad_scaled(x, g, w_shape, pad, row_scale):
-    """gw[n] = row_scale[n] * wgrad(x, g)[n] of a stride-1 layer; output placement as in _conv_wgrad_raw."""
-    return _conv_wgrad_raw(x, g, w_shape, 1, pad, row_scale=row_scale)
-
-
 def _winograd_dgrad_fused(g, U, out_scale, mask):
     """gx = mask > 0 ? (F(4x4,3x3) data gradient of a stride-1 / pad-1 3x3 layer * out_scale) : 0; U = winograd_filter_dgrad(w)."""
     B, Cout, H, W = g.shape
@@ -667,26 +641,23 @@ class _BottleneckFn(torch.autograd.Function):
     epilogue reads."""
 
     @staticmethod
-    def forward(ctx, x, w1, w2, w3, wd, s1, b1, s2, b2, s3, b3, sd, bd, in_relu, out_premasked, wino, stride=1):
+    def forward(ctx, x, w1, w2, w3, wd, s1, b1, s2, b2, s3, b3, sd, bd, in_relu, out_premasked, route2, stride=1):
         _need_cuda(x, w1, w2, w3)
         x = as_nhwc(x)
         w1, w2, w3 = as_nhwc(w1), as_nhwc(w2), as_nhwc(w3)
         a1 = _conv_fwd_raw(x, w1, s1, b1, None, stride, 0, EPI_SCALE | EPI_RELU)      # caffe style: the stride sits on conv1
         v2 = None
-        if wino:
-            a2 = conv3x3_winograd(a1, winograd_filter(w2.detach(), 4), s2, b2, True,
-                                  keep_v=WINOGRAD_KEEP_V and _winograd_wgrad_ok(a1, w2.shape, 1, 1))
-            if isinstance(a2, tuple):
-                a2, v2 = a2
+        if route2.fwd == WINOGRAD:
+            a2, v2 = _winograd_fwd(a1, winograd_filter(w2.detach(), 4), s2, b2, True, keep_v=route2.keep_v)
         else:
-            a2 = _conv_fwd_raw(a1, w2, s2, b2, None, 1, 1, EPI_SCALE | EPI_RELU)
+            a2 = _conv_fwd_raw(a1, w2, s2, b2, None, 1, 1, route2.flags)
         if wd is not None:
             wd = as_nhwc(wd)
             res = _conv_fwd_raw(x, wd, sd, bd, None, stride, 0, EPI_SCALE)
         else:
             res = x
         out = _conv_fwd_raw(a2, w3, s3, b3, res, 1, 0, EPI_SCALE | EPI_RESIDUAL | EPI_RELU)
-        ctx.flags = (bool(in_relu), bool(out_premasked), bool(wino), wd is not None)
+        ctx.flags = (bool(in_relu), bool(out_premasked), route2, wd is not None)
         ctx.stride = int(stride)
         ctx.save_for_backward(x, a1, a2, out, w1, w2, w3, wd, s1, s2, s3, sd, v2)
         return out
@@ -694,7 +665,7 @@ class _BottleneckFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         x, a1, a2, out, w1, w2, w3, wd, s1, s2, s3, sd, v2 = ctx.saved_tensors
-        in_relu, premasked, wino, has_ds = ctx.flags
+        in_relu, premasked, route2, has_ds = ctx.flags
         need = ctx.needs_input_grad
         g = as_nhwc(g)
         if premasked:
@@ -706,7 +677,7 @@ class _BottleneckFn(torch.autograd.Function):
         st = ctx.stride
         # ---- data gradients (the chain the rest of the backward waits for)
         g2 = _dgrad_fused(gpre, w3, a2.shape, 0, gy_scale=s3, out_scale=s2, mask=a2)         # gradient at conv2's raw output
-        if wino:
+        if route2.dgrad == WINOGRAD:
             g1 = _winograd_dgrad_fused(g2, winograd_filter_dgrad(w2), s1, a1)
         else:
             g1 = _dgrad_fused(g2, w2, a1.shape, 1, out_scale=s1, mask=a1)
@@ -719,8 +690,8 @@ class _BottleneckFn(torch.autograd.Function):
 
         # ---- filter gradients (conv3: gy = gpre * s3 as a per-row factor), on the side branch when the step has one
         def wgrads():
-            gw3 = _wgrad_scaled(a2, gpre, w3.shape, 0, s3) if need[3] else None
-            gw2 = _conv_wgrad_raw(a1, g2, w2.shape, 1, 1, winograd=wino, v=v2) if need[2] else None
+            gw3 = _conv_wgrad_raw(a2, gpre, w3.shape, 1, 0, row_scale=s3) if need[3] else None
+            gw2 = _conv_wgrad_raw(a1, g2, w2.shape, 1, 1, route=route2.wgrad, v=v2) if need[2] else None
             gw1 = _conv_wgrad_raw(x, g1, w1.shape, st, 0) if need[1] else None
             gwd = _conv_wgrad_raw(x, gpre, wd.shape, st, 0, row_scale=sd) if (has_ds and need[4]) else None
             return gw1, gw2, gw3, gwd
@@ -735,10 +706,12 @@ def bottleneck(x, w1, w2, w3, bn1, bn2, bn3, down=None, in_relu=False, out_prema
     the projection (caffe style), a strided block always has the projection."""
     if stride != 1 and down is None:
         raise ValueError("a strided bottleneck needs the projection on its skip branch")
-    wino = (WINOGRAD_TRAIN and w2.shape[1] >= WINOGRAD_TRAIN_MIN_C and w2.shape[0] >= WINOGRAD_TRAIN_MIN_C and w2.shape[1] % 4 == 0)
+    B, _, H, W = x.shape
+    route2 = _plan((B, w2.shape[1], (H - 1) // stride + 1, (W - 1) // stride + 1), w2.shape, 1, 1, scale=True, shift=True, relu=True,
+                   needs_w=torch.is_grad_enabled() and w2.requires_grad, in_block=True)
     wd, sd, bd = down if down is not None else (None, None, None)
     return _BottleneckFn.apply(x, w1, w2, w3, wd, bn1[0], bn1[1], bn2[0], bn2[1], bn3[0], bn3[1], sd, bd, bool(in_relu),
-                               bool(out_premasked), bool(wino), int(stride))
+                               bool(out_premasked), route2, int(stride))
 
 
 def conv2d(x, w, scale=None, shift=None, res=None, stride=1, pad=0, relu=False, winograd=False, out=None):
@@ -749,14 +722,11 @@ def conv2d(x, w, scale=None, shift=None, res=None, stride=1, pad=0, relu=False, 
     if out is not None:
         if torch.is_grad_enabled() and (x.requires_grad or w.requires_grad):
             raise ValueError("conv2d(out=...) is a forward-only path")
-        flags = (EPI_SCALE if scale is not None else EPI_BIAS if shift is not None else 0) | (EPI_RESIDUAL if res is not None else 0) | \
-            (EPI_RELU if relu else 0)
         _need_cuda(x, w)
         return _conv_fwd_raw(as_nhwc(x), as_nhwc(w), scale, shift, as_nhwc(res) if res is not None else None, int(stride), int(pad),
-                             flags, out=out)
-    if pad == 0 and KH == H and KW == W and (KH > 1 or KW > 1) and res is None:
-        # the filter covers the whole input (vrd.conv_lo's 8x8 layer): one output pixel, i.e. a linear layer
-        # over the NHWC-flattened map.  As a conv its dgrad is a full correlation with 63 of 64 taps masked.
+                             conv_route.epilogue_flags(scale is not None, shift is not None, res is not None, relu), out=out)
+    if conv_route.whole_filter_as_linear(x.shape, w.shape, pad, res is not None):
+        # one output pixel, i.e. a linear layer over the NHWC-flattened map
         xf = as_nhwc(x).permute(0, 2, 3, 1).reshape(B, H * W * Cin, 1, 1)
         wf = w.contiguous(memory_format=_CL).permute(0, 2, 3, 1).reshape(Cout, KH * KW * Cin, 1, 1)
         return _ConvFn.apply(xf, wf, scale, shift, None, 1, 0, bool(relu))
@@ -1409,14 +1379,14 @@ def winograd_filter_dgrad(w):
     return U
 
 
-# I2V_WINOGRAD_KEEP_V=0: a trained 3x3 layer transforms its input again for the filter gradient instead of keeping the forward's
-# transformed input (36/16 of the activation's size per layer, ~1.9 GB over the 33 layers of an 8-frame instance_styleD step)
-WINOGRAD_KEEP_V = True
+def conv3x3_winograd(x, U, scale=None, shift=None, relu=False):
+    """stride-1 / pad-1 3x3 convolution with a pre-transformed frozen filter U (ops.winograd_filter); forward only."""
+    return _winograd_fwd(x, U, scale, shift, relu)[0]
 
 
-def conv3x3_winograd(x, U, scale=None, shift=None, relu=False, tag="fwd", keep_v=False):
-    """stride-1 / pad-1 3x3 convolution with a pre-transformed frozen filter U (ops.winograd_filter); forward only.
-    ``keep_v`` (F(4x4,3x3) only): -> (y, V), V = the transformed input in a tensor of its own (for the filter gradient)."""
+def _winograd_fwd(x, U, scale=None, shift=None, relu=False, tag="fwd", keep_v=False):
+    """-> (y, V).  ``keep_v`` (F(4x4,3x3) only): V = the transformed input in a tensor of its own (for the filter gradient),
+    else None."""
     _need_cuda(x, U)
     x = as_nhwc(x)
     B, Cin, H, W = x.shape
@@ -1433,11 +1403,12 @@ def conv3x3_winograd(x, U, scale=None, shift=None, relu=False, tag="fwd", keep_v
     with _Timed(2.0 * B * H * W * Cout * 9 * Cin, tag,
                 "M%d N%d K%d (3x3 winograd F%d) gemmMB=%.2f" % (B * H * W, Cout, 9 * Cin, 4 if four else 2, gemm_mb),
                 4 * (x.numel() + 9 * Cout * Cin + y.numel())):
+        v = None
         if keep_v and four:
             v = torch.empty((lib.i2v_conv3x3_winograd4_v_bytes(B, H, W, Cin) // 4,), device=x.device, dtype=torch.float32)
             check(lib.i2v_conv3x3_winograd4_fwd_keep(ptr(x), ptr(U), ptr(scale), ptr(shift), ptr(y), ptr(v), B, H, W, Cin, Cout,
                                                      int(bool(relu)), ptr(ws), ws.numel(), stream()), "conv3x3_winograd4_fwd_keep")
-            return y, v
-        check(fn(ptr(x), ptr(U), ptr(scale), ptr(shift), ptr(y), B, H, W, Cin, Cout, int(bool(relu)), ptr(ws), ws.numel(),
-                 stream()), "conv3x3_winograd_fwd")
-    return (y, None) if keep_v else y
+        else:
+            check(fn(ptr(x), ptr(U), ptr(scale), ptr(shift), ptr(y), B, H, W, Cin, Cout, int(bool(relu)), ptr(ws), ws.numel(),
+                     stream()), "conv3x3_winograd_fwd")
+    return y, v

@@ -27,6 +27,10 @@ def oracle():
 
 
 DEV = "cuda:0"
+# what the conv / linear layers are held to against torch: the direct kernels element by element, the Winograd F(4x4,3x3) path
+# (transform constants up to 8 and down to 1/24 in fp32) by its largest error over the reference's largest element
+DIRECT_TOL = dict(rtol=3e-4, atol=3e-4)
+WINOGRAD_REL = 1e-4
 
 
 def _rel_err(a, b):
@@ -469,7 +473,7 @@ def test_conv_bwd_vs_torch_autograd(ops, case):
     xd, wd, bd = (torch.from_numpy(a).to(DEV).requires_grad_() for a in (x, w, b))
     y = ops.conv2d(xd, wd, None, bd, None, s, p, relu=True)
     y.backward(gy.to(DEV))
-    tol = dict(rtol=3e-4, atol=3e-4)
+    tol = DIRECT_TOL
     np.testing.assert_allclose(xd.grad.cpu().numpy(), xt.grad.numpy(), **tol)
     # eligible 3x3 layers take the Winograd F(4x4,3x3) filter gradient: fp32 error ~2e-5 of the tensor's range (the
     # transform constants reach 8 and 1/24), where the direct kernel has ~1e-6
@@ -515,14 +519,14 @@ def test_trained_3x3_winograd_fwd_and_dgrad_vs_torch_autograd(ops, B, C, N, H, W
     xd, wd = x.detach().double().requires_grad_(), w.detach().double().requires_grad_()
     pre = F.conv2d(xd, wd, padding=1) * sc.double().view(1, -1, 1, 1) + sh.double().view(1, -1, 1, 1)
     rel = lambda a, b: ((a.double() - b).abs().max() / b.abs().max()).item()
-    assert rel(y, torch.relu(pre.detach())) < 1e-4
+    assert rel(y, torch.relu(pre.detach())) < WINOGRAD_REL
     # the ReLU mask is the kernel's own: an output within ~1e-5 of zero may sit on the other side of the ReLU in fp32,
     # and one flipped element moves the input gradient by a whole tap -- masks must agree everywhere else
     mask = y.detach() > 0
     flips = (mask != (pre.detach() > 0))
     assert not bool((flips & (pre.detach().abs() > 1e-4 * pre.detach().abs().max())).any())
     (pre * mask * gy.double()).sum().backward()
-    assert rel(x.grad, xd.grad) < 1e-4 and rel(w.grad, wd.grad) < 1e-4
+    assert rel(x.grad, xd.grad) < WINOGRAD_REL and rel(w.grad, wd.grad) < WINOGRAD_REL
     # the same layer with the direct kernels (the default of ops.conv2d)
     x2, w2 = x.detach().clone().requires_grad_(), w.detach().clone().requires_grad_()
     y2 = ops.conv2d(x2, w2, sc, sh, None, 1, 1, relu=True)
@@ -546,7 +550,7 @@ def test_linear_fwd_bwd(ops, M, K, N):
     xd, wd, bd = (torch.from_numpy(a).to(DEV).requires_grad_() for a in (x, w, b))
     y = ops.linear(xd, wd, bd, relu=True)
     y.backward(gy.to(DEV))
-    tol = dict(rtol=3e-4, atol=3e-4)
+    tol = DIRECT_TOL
     np.testing.assert_allclose(y.detach().cpu().numpy(), ref.detach().numpy(), **tol)
     np.testing.assert_allclose(xd.grad.cpu().numpy(), xt.grad.numpy(), **tol)
     np.testing.assert_allclose(wd.grad.cpu().numpy(), wt.grad.numpy(), **tol)
@@ -1211,7 +1215,7 @@ def test_conv_dgrad_fused_and_wgrad_scaled_vs_torch():
         assert float((got - want).abs().max()) <= 1e-4 * float(want.abs().max()), (cin, cout, k)
         plain = ops._dgrad_fused(gy, w, x.shape, pad)
         assert float((plain - F.conv_transpose2d(gy, w, None, 1, pad)).abs().max()) <= 1e-4 * float(plain.abs().max())
-        gw = ops._wgrad_scaled(x, gy, w.shape, pad, gs)
+        gw = ops._conv_wgrad_raw(x, gy, w.shape, 1, pad, row_scale=gs)
         wref = torch.nn.grad.conv2d_weight(x, w.shape, gy, 1, pad) * gs.view(-1, 1, 1, 1)
         assert float((gw - wref).abs().max()) <= 1e-4 * float(wref.abs().max()), (cin, cout, k)
 
@@ -1227,11 +1231,11 @@ def test_winograd_filter_gradient_vs_torch(B, C, N, H, W):
     rs = torch.rand(N, device=DEV) + 0.5
     want = torch.nn.grad.conv2d_weight(x.double(), (N, C, 3, 3), g.double(), 1, 1)
     scale = float(want.abs().max())
-    got = ops._conv_wgrad_raw(x, g, (N, C, 3, 3), 1, 1, winograd=True)
+    got = ops._conv_wgrad_raw(x, g, (N, C, 3, 3), 1, 1, route=ops._wgrad_route((N, C, 3, 3), 1, 1))
     direct = ops._conv_wgrad_raw(x, g, (N, C, 3, 3), 1, 1)
     assert float((direct.double() - want).abs().max()) <= 1e-4 * scale
     assert float((got.double() - want).abs().max()) <= 2e-4 * scale, float((got.double() - want).abs().max()) / scale
-    got = ops._conv_wgrad_raw(x, g, (N, C, 3, 3), 1, 1, winograd=True, row_scale=rs)
+    got = ops._conv_wgrad_raw(x, g, (N, C, 3, 3), 1, 1, route=ops._wgrad_route((N, C, 3, 3), 1, 1), row_scale=rs)
     assert float((got.double() - want * rs.double().view(-1, 1, 1, 1)).abs().max()) <= 2e-4 * 1.5 * scale
 
 
@@ -1272,6 +1276,7 @@ def test_filter_gradient_lds_dma_staging_is_bit_equal(B, C, N, H, W):
     filter gradient uses; both within 1e-5 of float64 torch."""
     from i2vsgg_amd import launch, ops
     from i2vsgg_amd._lib import TUNE, lib
+    from i2vsgg_amd.conv_route import WINOGRAD_X
     torch.manual_seed(11)
     cl = lambda t: t.contiguous(memory_format=torch.channels_last)
     x, g = cl(torch.randn(B, C, H, W, device=DEV)), cl(torch.randn(B, N, H, W, device=DEV))
@@ -1288,8 +1293,8 @@ def test_filter_gradient_lds_dma_staging_is_bit_equal(B, C, N, H, W):
                 assert lib.i2v_set_tuning(keys[0], dma) == 0 and lib.i2v_set_tuning(keys[1], tiles) == 0
                 with ctx, torch.no_grad():
                     got[dma] = (ops._conv_wgrad_raw(x, g, (N, C, 1, 1), 1, 0).clone(),
-                                ops._conv_wgrad_raw(x, g, (N, C, 3, 3), 1, 1, winograd=True).clone()
-                                if ops._winograd_wgrad_ok(x, (N, C, 3, 3), 1, 1) else None)
+                                ops._conv_wgrad_raw(x, g, (N, C, 3, 3), 1, 1, route=WINOGRAD_X).clone()
+                                if ops._wgrad_route((N, C, 3, 3), 1, 1) == WINOGRAD_X else None)
             assert torch.equal(got[0][0], got[1][0]), (tiles, float((got[0][0] - got[1][0]).abs().max()))
             assert float((got[1][0].double() - want).abs().max()) <= 1e-5 * scale
             if got[0][1] is not None:
@@ -1608,6 +1613,7 @@ def test_every_planned_form_and_finish_runs_once(ops):
     from test_conv_plan_host import FWD_FINISHES, FWD_FORMS, TABLE, WGRAD_FINISHES, plan_of, tuned
     from i2vsgg_amd import launch
     from i2vsgg_amd._lib import lib, ptr, stream
+    from i2vsgg_amd.conv_route import DIRECT
     WS = launch.SplitWorkspace.BYTES
     with open(TABLE) as f:
         rows = [r for r in json.load(f)["rows"] if r["plan"][0] == 0]
@@ -1665,8 +1671,9 @@ def test_every_planned_form_and_finish_runs_once(ops):
         ordered = fin in (WGRAD_FINISHES["ORDERED_TILES"], WGRAD_FINISHES["ORDERED_PARTS"], WGRAD_FINISHES["EXTERNAL_PARTS"])
         with tuned(lib, row):
             assert plan_of(lib, row) == row["plan"]
-            gw = ops._conv_wgrad_raw(x, g, (Cout, Cin, KH, KW), stride, pad, winograd=ext).clone()
-            again = ops._conv_wgrad_raw(x, g, (Cout, Cin, KH, KW), stride, pad, winograd=ext) if ordered else None
+            route = ops._wgrad_route((Cout, Cin, KH, KW), stride, pad) if ext else DIRECT
+            gw = ops._conv_wgrad_raw(x, g, (Cout, Cin, KH, KW), stride, pad, route=route).clone()
+            again = ops._conv_wgrad_raw(x, g, (Cout, Cin, KH, KW), stride, pad, route=route) if ordered else None
         ref = torch.nn.grad.conv2d_weight(x.double(), (Cout, Cin, KH, KW), g.double(), stride, pad)
         err, scale = float((gw.double() - ref).abs().max()), float(ref.abs().max())
         bound = 2e-4 if ext else 2e-6 if ordered else 2e-5
@@ -1678,7 +1685,7 @@ def test_every_planned_form_and_finish_runs_once(ops):
             np.testing.assert_allclose(gw.cpu().numpy(), ref.float().cpu().numpy(), rtol=2e-5, atol=2e-5)
         if ext:                      # the same transforms, the planes' parts summed by atomics (the default context's call form)
             assert lib.i2v_get_tuning(4) == 2
-            plain = ops._conv_wgrad_raw(x, g, (Cout, Cin, KH, KW), stride, pad, winograd=True)
+            plain = ops._conv_wgrad_raw(x, g, (Cout, Cin, KH, KW), stride, pad, route=route)
             diff = float((plain - gw).abs().max())
             record_margin("test_every_planned_form_and_finish_runs_once", "wgrad external parts vs atomics", diff / scale, 2e-5)
             assert diff <= 2e-5 * scale, (row, diff, scale)
