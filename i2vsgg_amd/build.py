@@ -6,8 +6,8 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libi2vsgg_hip.so")
-SOURCES = ["api.cpp", "roi_ops.hip", "rpn.hip", "conv.hip", "heads.hip", "image.hip", "winograd.hip", "dstyle.hip", "video.hip",
-           "det_eval.hip"]
+SOURCES = ["api.cpp", "roi_ops.hip", "rpn.hip", "conv.hip", "wgrad.hip", "elementwise.hip", "heads.hip", "image.hip", "winograd.hip",
+           "dstyle.hip", "video.hip", "det_eval.hip"]
 # -ffp-contract=off: box / IoU / ROIAlign arithmetic must round once per operation like the
 # reference's CPU path (no FMA contraction), or NMS threshold decisions can flip.
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-ffp-contract=off", "-fno-fast-math",
@@ -15,7 +15,8 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-ffp-contract=o
 # MFMA accumulators in VGPRs, not AGPRs: measured on MI355X (tools/micro/mfma_rate.hip, tools/conv_ablate.py) a
 # back-to-back v_mfma_f32_16x16x4_f32 stream issues every 32 cycles with VGPR accumulators but only every ~45
 # cycles in the AGPR form hipcc picks by default for these kernels.
-EXTRA = {"conv.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"], "dstyle.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"]}
+# The files with MFMA kernels get the flag (elementwise.hip has none: its kernels assemble to the same instructions either way).
+EXTRA = {src: ["-mllvm", "-amdgpu-mfma-vgpr-form"] for src in ("conv.hip", "wgrad.hip", "dstyle.hip")}
 
 
 STAMP = os.path.join(HERE, "build", "stamp.json")
@@ -73,7 +74,7 @@ def build(force=False, verbose=False):
     for src in SOURCES:
         path = os.path.join(CSRC, src)
         if not os.path.exists(path):
-            continue
+            raise RuntimeError("source %s named in SOURCES does not exist" % path)
         obj = os.path.join(objdir, src.rsplit(".", 1)[0] + ".o")
         objs.append(obj)
         cmd = [hipcc] + FLAGS + EXTRA.get(src, []) + (["-x", "hip"] if src.endswith(".cpp") else []) + ["-c", path, "-o", obj]

@@ -1,8 +1,8 @@
-// The launch plans of csrc/conv.hip: which tile, split, finish and kernel form a forward / data-gradient GEMM
+// The launch plans of csrc/conv.hip and csrc/wgrad.hip: which tile, split, finish and kernel form a forward / data-gradient GEMM
 // (plan_conv_fwd) or a filter-gradient GEMM (plan_wgrad) takes.  Host-only and pure: no HIP, no globals -- the tuning
 // table (g_i2v_tuning, indexed by I2V_TUNE_*) and the forced tile come in as arguments, so a plan is a function of its
 // arguments that the host tests check without a GPU (tests/test_conv_plan_host.py against tests/golden/conv_plans.json).
-// The launchers in conv.hip only bind pointers, clear and switch on what these functions return.
+// The launchers (run_conv in conv.hip, launch_wgrad in wgrad.hip) only bind pointers, clear and switch on what these functions return.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>

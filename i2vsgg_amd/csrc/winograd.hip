@@ -10,9 +10,7 @@
 //   y(tile t)    = A^T M[.][t][n] A          output transform + BN scale/shift + ReLU  (streaming)
 // xi = 4*row + col of the 4x4 transform domain.  Only the GEMM uses the matrix cores; the two transforms are
 // streaming kernels that overlap with MFMA work of the other stream.
-#include "common.h"
-#include "conv_plan.h"
-#include <algorithm>
+#include "conv_common.h"
 
 extern "C" int32_t i2v_gemm_tn_batched(const float* x, const float* gy, float* gw, int32_t M, int32_t N, int32_t K,
                                        int32_t nbatch, long long stride_x, long long stride_gy, long long stride_gw,

@@ -80,7 +80,7 @@ def _entry_takes(M, K, N):
 
 
 def _persistent(M, K, N):
-    """launch_fc_update's conditions (csrc/conv.hip) for a linear problem the entry point takes: at most 256 rows, N and K
+    """launch_fc_update's conditions (csrc/wgrad.hip) for a linear problem the entry point takes: at most 256 rows, N and K
     multiples of 4, every operand below 2 GiB.  Returns the stage count NS it instantiates, or 0 for the tiled fallback."""
     assert _entry_takes(M, K, N)
     ok = M <= 256 and N % 4 == 0 and K % 4 == 0 and 4 * max(M * K, M * N, N * K) < 1 << 31

@@ -38,8 +38,8 @@ def _weights_close(got, want, what, l2=1e-5, peak=1e-5):
     Round 4 had to allow 1e-4 element-wise: the small FCs of the relation head accumulated their split-K partials with fp32
     atomics, so a pre-activation within rounding of zero could land on either side of its ReLU from one run to the next (seen
     once in five suite runs: 1.5e-5).  Round 5 removed the cause -- every split reduction of the step is summed in a fixed
-    order (csrc/conv.hip: split-K finish for any split count, ordered filter-gradient and bias-column sums;
-    test_sgg_step_is_bit_reproducible) -- and the bound is back at 1e-5.  Every deviation above 1e-6 is still logged with its
+    order (csrc/conv.hip: split-K finish for any split count; csrc/wgrad.hip and csrc/elementwise.hip: ordered
+    filter-gradient and bias-column sums; test_sgg_step_is_bit_reproducible) -- and the bound is back at 1e-5.  Every deviation above 1e-6 is still logged with its
     shape (how many filter rows / columns carry it) to gpurun_out/weights_deviation.log, pass or fail."""
     got, want = np.asarray(got, np.float64), np.asarray(want, np.float64)
     d = np.abs(got - want)
