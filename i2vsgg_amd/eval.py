@@ -297,7 +297,8 @@ class RelationStep(_FrameGraphStep):
             rois[f, cb:cb + len(ixs), 1:] = union
             bounds[f, :len(ixs)] = bnd
             ix[f, 0, :len(ixs)], ix[f, 1, :len(ixs)] = ixs, ixo
-            conf[f, :nb] = 1                                            # :608 every annotated box enters with confidence 1
+            # :608 every annotated box enters with confidence 1; tracked detections carry their own (lib/utils.py:611)
+            conf[f, :nb] = np.asarray(a["scores"], np.float32).reshape(nb) if "scores" in a else 1
             meta.append((np.array(a["boxes"], np.float64).reshape(-1, 4), np.asarray(a["box_classes"]), ixs, ixo))
         self.inputs.write_host({"rois": rois, "bounds": bounds, "ix": ix, "conf": conf})
         self._meta = meta

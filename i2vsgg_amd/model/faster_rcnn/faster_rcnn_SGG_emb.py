@@ -115,7 +115,10 @@ class _fasterRCNN(nn.Module):
         ih, iw, sc = float(info[0][0]), float(info[0][1]), float(info[0][2])
         detected = anno["boxes"]
         classes = list(anno["box_classes"])
-        scores = [1 for _ in classes]
+        # annotated boxes enter with confidence 1; tracked detections (seqnms.to_annotations) carry their own (lib/utils.py:611)
+        scores = [float(s) for s in anno["scores"]] if "scores" in anno else [1 for _ in classes]
+        if len(scores) != len(classes):
+            raise ValueError("annotation of %s: %d scores for %d boxes" % (im_path, len(scores), len(classes)))
         if len(detected) == 0:
             return {"bboxes": [], "classes": [], "scores": []}
         if len(detected) == 1:

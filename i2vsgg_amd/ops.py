@@ -1111,6 +1111,33 @@ def video_viou_match(pred_off, pred_rel, pred_score, gt_off, gt_rel, boxes, viou
     return ov, hit, hit_ov
 
 
+def seq_nms(group_off, frame_no, box_off, box, score, link_iou=0.5, nms_iou=0.3, rescore="avg", device=None):
+    """Seq-NMS of a packed batch of (video, class) groups in one launch (include/i2vsgg_hip.h, i2v_seqnms; ``seqnms.pack``
+    builds the arrays).  Arrays or tensors: group_off (G+1), frame_no (F), box_off (F+1) int32, box (N,4) fp32, score (N)
+    fp32.  Returns device tensors (tid (N) int32, new_score (N) fp32, n_tracks (G) int32)."""
+    dev = torch.device(device if device is not None else "cuda")
+    if dev.type != "cuda":
+        raise _lib.I2VError("i2vsgg_amd ops run on the GPU only (got device %s); seqnms.seq_nms(device=None) is the host form" % dev)
+    if rescore not in ("avg", "max"):
+        raise ValueError("seq_nms: rescore is 'avg' or 'max' (got %r)" % (rescore,))
+    group_off, frame_no, box_off = (_to_dev(x, torch.int32, dev) for x in (group_off, frame_no, box_off))
+    box, score = _to_dev(box, torch.float32, dev), _to_dev(score, torch.float32, dev)
+    G, F, N = group_off.numel() - 1, frame_no.numel(), score.numel()
+    if G < 0 or box_off.numel() != F + 1 or box.numel() != 4 * N:
+        raise ValueError("seq_nms: array sizes do not agree")
+    tid = torch.full((N,), -1, device=dev, dtype=torch.int32)
+    new_score = score.clone()
+    n_tracks = torch.zeros((G,), device=dev, dtype=torch.int32)
+    with torch.cuda.device(dev):
+        ws = launch.workspace(lib.i2v_seqnms_workspace_bytes(G, F, N), dev, "seqnms")
+        check(lib.i2v_seqnms(ptr(group_off), ptr(frame_no), ptr(box_off), ptr(box), ptr(score), G, F, N, float(link_iou),
+                             float(nms_iou), 1 if rescore == "max" else 0, ptr(tid), ptr(new_score), ptr(n_tracks),
+                             ptr(ws), ws.numel(), stream()), "seq_nms")
+        if G > 0:
+            _video_status(ws, "seq_nms", "group")
+    return tid, new_score, n_tracks
+
+
 def _det_eval_device(device, what):
     dev = torch.device(device if device is not None else "cuda")
     if dev.type != "cuda":

@@ -247,6 +247,30 @@ int32_t i2v_video_viou_match(const int32_t* pred_off, const int32_t* pred_rel, c
                              int32_t max_gt, double viou_threshold, double* ov, int32_t* hit, double* hit_ov,
                              void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- Seq-NMS: per-frame detections of one class linked into object tracks (Han et al., 2016) ---------------------
+ * The stage between the detector's all_boxes and the boxes the relation loop reads; the reference ran it outside its
+ * tree (test_net_instance_styleD_bilinear.py:209-211 dumps its input, faster_rcnn_SGG_emb.py:460-474 reads its output),
+ * so the rules are this project's own and are stated in full in i2vsgg_amd/seqnms.py.  One workgroup of one wave per
+ * group = (video, class), lane a = box a of the current frame.
+ *   group_off (n_groups+1): group g owns the frame slots [group_off[g], group_off[g+1]), in ascending frame number (a
+ *   video's frame without boxes of the class is a slot with zero boxes); frame_no (n_frames); box_off (n_frames+1): slot
+ *   f owns boxes [box_off[f], box_off[f+1]), at most 64; box (n_boxes x 4 fp32: x1 y1 x2 y2), score (n_boxes fp32).
+ * Inputs are widened to fp64 exactly; overlaps use the +1 convention of lib/model/nms/nms_cpu.py:14,26-31.  Box a of slot
+ * t links to box b of slot t+1 when frame_no[t+1] == frame_no[t] + 1 and overlap >= link_iou.  A pass runs, over the boxes
+ * still alive, best[t][a] = score[a] + max best[t+1][b] over alive linked b (lowest b on ties; score[a] alone without
+ * one), starts at the alive box of largest best (then lowest t, then lowest a) and follows the links.  The path's boxes
+ * get track id k = 0, 1, ... in extraction order and one new score: rescore 0 = the fp64 sum of their scores in frame
+ * order / their number, rounded to fp32; 1 = their maximum.  They leave the alive set, with every alive box of the same
+ * slot whose overlap with the path's box is > nms_iou.  Passes repeat until no box is alive.
+ * Outputs: tid (n_boxes; -1: suppressed), new_score (n_boxes; a suppressed box keeps its score), n_tracks (n_groups).
+ * The first int32 of the workspace is a status word: 0, or 1 + the index of a group whose table entries were out of
+ * range (such a group is not touched; its n_tracks is 0). */
+size_t  i2v_seqnms_workspace_bytes(int32_t n_groups, int32_t n_frames, int32_t n_boxes);
+int32_t i2v_seqnms(const int32_t* group_off, const int32_t* frame_no, const int32_t* box_off, const float* box,
+                   const float* score, int32_t n_groups, int32_t n_frames, int32_t n_boxes, double link_iou,
+                   double nms_iou, int32_t rescore, int32_t* tid, float* new_score, int32_t* n_tracks,
+                   void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- VOC detection evaluation that ends the detector test loop (lib/datasets/voc_eval.py:132-212) ----------------
  * Detections lie in results-file order (class, then image, then row; i2vsgg_amd/detection_eval.py pack()): det_key
  * (n_det int32) is the score as the results file would hold it ('%.3f'), in thousandths; det_box (n_det x 4 fp64) the

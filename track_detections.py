@@ -1,0 +1,67 @@
+#!/usr/bin/env python3
+"""Link pickled detections into object tracks (Seq-NMS, ``i2vsgg_amd.seqnms``): the stage between the detector test loop and
+the relation test loop.  ``--detections`` is the ``detections.pkl`` that ``test_instance_styled.py`` writes,
+``all_boxes[class][image]``; ``--imdbval_name`` names the imdb it was run on.  Two files are written beside it (or into
+``--output_dir``): ``detections_seqnms.pkl``, the rescored survivors in the same layout (``eval_detections.py`` reads it), and
+``tracked_boxes.pkl``, {frame file name: {boxes, box_classes, scores, tids, rels: []}}, which ``test_sgg_emb.py`` /
+``video_sgg_emb.py`` take as ``--target_gt_rels_path``.  Frames map to (video, frame number) as in ``video_sgg_emb.py``: the
+frames in the order of their paths, every ``--frames_per_video`` consecutive ones a video (default: one video).  The linking
+runs on the GPU; ``--cpu`` runs the same rules on the host."""
+import argparse
+import os
+import pickle
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, ROOT)
+os.environ.setdefault("DEBUG_CLR_GRAPH_PACKET_CAPTURE", "0")     # before HIP initialises: i2vsgg_amd/__init__.py
+
+
+def main(argv=None):
+    p = argparse.ArgumentParser(description="Seq-NMS over pickled detections")
+    p.add_argument("--detections", required=True)
+    p.add_argument("--imdbval_name", required=True)
+    p.add_argument("--frames_per_video", type=int, default=0)
+    p.add_argument("--link_iou", type=float, default=0.5)
+    p.add_argument("--nms_iou", type=float, default=0.3)
+    p.add_argument("--rescore", default="avg", choices=["avg", "max"])
+    p.add_argument("--score_thresh", type=float, default=0.0, help="detections below it take no part")
+    p.add_argument("--min_score", type=float, default=0.7, help="tracked_boxes.pkl: a box needs a new score above it")
+    p.add_argument("--max_per_class", type=int, default=10, help="tracked_boxes.pkl: boxes per frame and class")
+    p.add_argument("--min_len", type=int, default=1, help="tracked_boxes.pkl: members a track needs")
+    p.add_argument("--cpu", action="store_true", help="host implementation (no GPU needed)")
+    p.add_argument("--output_dir", default=None)
+    a = p.parse_args(argv)
+    from i2vsgg_amd import seqnms
+    from i2vsgg_amd.roi_data_layer.roidb import get_imdb
+    with open(a.detections, "rb") as f:
+        all_boxes = pickle.load(f)
+    imdb = get_imdb(a.imdbval_name)
+    n = len(all_boxes[0]) if len(all_boxes) else 0
+    paths = [imdb.image_path_at(i) for i in range(n)]
+    per = a.frames_per_video if a.frames_per_video > 0 else max(n, 1)
+    index = dict((path, (str(k // per), k % per)) for k, path in enumerate(sorted(paths)))
+    frame_index = [index[path] for path in paths]
+    t0 = time.time()
+    out, tracks = seqnms.seq_nms(all_boxes, frame_index, a.link_iou, a.nms_iou, a.rescore, a.score_thresh,
+                                 device=None if a.cpu else "cuda:0")
+    dt = time.time() - t0
+    anno = seqnms.to_annotations(out, tracks, [path.split("/")[-1] for path in paths], a.min_score, a.max_per_class, a.min_len,
+                                 frame_index)
+    count = lambda ab: sum(len(c) for row in ab[1:] for c in row)
+    n_tracks = sum(len(set((frame_index[i][0], int(t)) for i in range(n) for t in tracks[j][i])) for j in range(len(tracks)))
+    print("seq-nms: %d videos, %d classes, %d detections -> %d on %d tracks, %.1f ms; %d boxes for the relation loop" % (
+        len(set(v for v, _ in frame_index)), max(len(all_boxes) - 1, 0), count(all_boxes), count(out), n_tracks, 1e3 * dt,
+        sum(len(e["boxes"]) for e in anno.values())))
+    out_dir = a.output_dir or os.path.dirname(os.path.abspath(a.detections))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, obj in (("detections_seqnms.pkl", out), ("tracked_boxes.pkl", anno)):
+        with open(os.path.join(out_dir, name), "wb") as f:
+            pickle.dump(obj, f, pickle.HIGHEST_PROTOCOL)
+        print("wrote %s" % os.path.join(out_dir, name))
+    return out, tracks, anno
+
+
+if __name__ == "__main__":
+    main()
