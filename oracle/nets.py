@@ -104,13 +104,25 @@ def netd_style(x, p, lam=1.0, context=False, dim=512, rank=5):
     return (d, z) if context else d
 
 
-def _fc(x, p, k, relu=True):
+def _tap(taps, k, z):
+    """Keep a pre-activation under its layer name (``vrd.fc6`` -> ``fc6``); a layer that runs twice (fc6 / fc7: boxes, then
+    union boxes) keeps its rows in call order."""
+    if taps is not None:
+        k = k[len("vrd."):] if k.startswith("vrd.") else k
+        taps[k] = z if k not in taps else torch.cat((taps[k], z), 0)
+
+
+def _fc(x, p, k, relu=True, taps=None):
     y = F.linear(x, p[k + ".fc.weight"], p[k + ".fc.bias"])
+    if relu:
+        _tap(taps, k, y)
     return F.relu(y) if relu else y
 
 
-def _convrelu(x, p, k, stride, pad):
-    return F.relu(F.conv2d(x, p[k + ".conv.weight"], p[k + ".conv.bias"], stride=stride, padding=pad))
+def _convrelu(x, p, k, stride, pad, taps=None):
+    y = F.conv2d(x, p[k + ".conv.weight"], p[k + ".conv.bias"], stride=stride, padding=pad)
+    _tap(taps, k, y)
+    return F.relu(y)
 
 
 def relative_loc(a, b):
@@ -123,38 +135,45 @@ def relative_loc(a, b):
     return np.hstack((xy, wh))
 
 
-def vrd_head(fmap, boxes, rel_boxes, spatial, ix_s, ix_o, prd_vecs, p, training=True, use_obj_visual=True, spatial_type=2):
+def vrd_head(fmap, boxes, rel_boxes, spatial, ix_s, ix_o, prd_vecs, p, training=True, use_obj_visual=True, spatial_type=2,
+             dtype=torch.float32, taps=None):
     """vrd.forward (resnet_SGG_emb.py:128-221), dropout disabled (eval-mode dropout
     for reproducibility, SURVEY.md section 7).  fmap (1,1024,H,W) NCHW numpy/torch;
     boxes (nb,5), rel_boxes (nr,5), spatial (nr,2,32,32) -- (nr,8) for spatial_type 1 (:172-174); returns (scores, rel_feat).
     ``use_obj_visual`` / ``spatial_type``: the branches of :166-180.
-    ``training`` only selects whether the final softmax is applied (:216-219)."""
+    ``training`` only selects whether the final softmax is applied (:216-219).
+    ``dtype``: the arithmetic of everything behind the ROI pool (the pool selects float32 maxima: exact in any type);
+    ``p`` must hold tensors of that type.  float64 is the high-precision form the parity tests measure against.
+    ``taps`` (a dict): filled with every ReLU / LeakyReLU pre-activation, keyed by layer name (``fc6`` .. ``conv_lo.0`` ..
+    ``prd_sem_embeddings.0``)."""
     fmap = torch.as_tensor(fmap, dtype=torch.float32)
     fm = fmap.numpy()
 
     def pool(rois):
         out, _ = cops.roi_pool_fwd(fm, np.asarray(rois, np.float32), 7, 7, 1.0 / 16.0)
-        return torch.from_numpy(out).reshape(out.shape[0], -1)
+        return torch.from_numpy(out).reshape(out.shape[0], -1).to(dtype)
 
     ix_s = torch.as_tensor(np.asarray(ix_s), dtype=torch.long)
     ix_o = torch.as_tensor(np.asarray(ix_o), dtype=torch.long)
-    x_so = _fc(_fc(pool(boxes), p, "vrd.fc6"), p, "vrd.fc7")
-    obj = _fc(x_so, p, "vrd.so_vis_embeddings", relu=False)
+    fc = lambda x, k, relu=True: _fc(x, p, k, relu, taps)
+    x_so = fc(fc(pool(boxes), "vrd.fc6"), "vrd.fc7")
+    obj = fc(x_so, "vrd.so_vis_embeddings", relu=False)
     x_s, x_o = obj.index_select(0, ix_s), obj.index_select(0, ix_o)
-    x = _fc(_fc(_fc(pool(rel_boxes), p, "vrd.fc6"), p, "vrd.fc7"), p, "vrd.fc8")
+    x = fc(fc(fc(pool(rel_boxes), "vrd.fc6"), "vrd.fc7"), "vrd.fc8")
     if use_obj_visual:
-        x = torch.cat((x, _fc(torch.cat((x_s, x_o), 1), p, "vrd.fc_so")), 1)
-    lo = torch.as_tensor(np.asarray(spatial), dtype=torch.float32)
+        x = torch.cat((x, fc(torch.cat((x_s, x_o), 1), "vrd.fc_so")), 1)
+    lo = torch.as_tensor(np.asarray(spatial), dtype=dtype)
     if spatial_type == 1:
-        x = torch.cat((x, _fc(lo.reshape(lo.size(0), -1), p, "vrd.fc_lov")), 1)
+        x = torch.cat((x, fc(lo.reshape(lo.size(0), -1), "vrd.fc_lov")), 1)
     elif spatial_type == 2:
-        lo = _convrelu(lo, p, "vrd.conv_lo.0", 2, 2)
-        lo = _convrelu(lo, p, "vrd.conv_lo.1", 2, 2)
-        lo = _convrelu(lo, p, "vrd.conv_lo.2", 1, 0)
-        x = torch.cat((x, _fc(lo.reshape(lo.size(0), -1), p, "vrd.fc_lov")), 1)
-    x = _fc(_fc(x, p, "vrd.fc_fusion"), p, "vrd.fc_rel", relu=False)
-    sem = torch.as_tensor(prd_vecs, dtype=torch.float32)
+        lo = _convrelu(lo, p, "vrd.conv_lo.0", 2, 2, taps)
+        lo = _convrelu(lo, p, "vrd.conv_lo.1", 2, 2, taps)
+        lo = _convrelu(lo, p, "vrd.conv_lo.2", 1, 0, taps)
+        x = torch.cat((x, fc(lo.reshape(lo.size(0), -1), "vrd.fc_lov")), 1)
+    x = fc(fc(x, "vrd.fc_fusion"), "vrd.fc_rel", relu=False)
+    sem = torch.as_tensor(prd_vecs, dtype=dtype)
     sem = F.linear(sem, p["vrd.prd_sem_embeddings.0.weight"], p["vrd.prd_sem_embeddings.0.bias"])
+    _tap(taps, "vrd.prd_sem_embeddings.0", sem)
     sem = F.leaky_relu(sem, 0.1)
     sem = F.linear(sem, p["vrd.prd_sem_embeddings.2.weight"], p["vrd.prd_sem_embeddings.2.bias"])
     scores = F.normalize(x, p=2, dim=1) @ F.normalize(sem, p=2, dim=1).t()

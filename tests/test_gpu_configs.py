@@ -690,7 +690,7 @@ def test_sgg_step_full_size_vs_oracle(fresh_cfg):
 
     # ---------------- the captured / overlapped step on the same batch
     eager = [loss] + [float(step()) for _ in range(2)]
-    w_eager = net.vrd.fc7.fc.weight.detach().cpu().numpy().copy()
+    w_eager = {n: p.detach().clone() for n, p in net.named_parameters() if n.startswith("vrd.")}      # all 26, on the device
     step.opt.unfuse()
     del step, net
     torch.cuda.empty_cache()
@@ -701,5 +701,8 @@ def test_sgg_step_full_size_vs_oracle(fresh_cfg):
     torch.cuda.synchronize()
     for a, b in zip(eager, cap):
         assert abs(a - b) <= 1e-5 * abs(a), (eager, cap)
-    _weights_close(net.vrd.fc7.fc.weight.detach().cpu().numpy(), w_eager, "configs[1] captured vs eager")
+    assert len(w_eager) == 26
+    for n, p in net.named_parameters():
+        if n.startswith("vrd."):
+            _weights_close(p, w_eager[n], "configs[1] captured vs eager, " + n)
     step.opt.unfuse()

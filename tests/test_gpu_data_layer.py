@@ -35,6 +35,12 @@ def _rel(a, b):
     return float(np.abs(a - b).max() / max(np.abs(b).max(), 1e-30))
 
 
+def _rel_dev(a, b):
+    """``_rel`` of two device tensors, computed where they live (in float64)."""
+    a, b = a.detach().double(), b.detach().double()
+    return float((a - b).abs().max()) / max(float(b.abs().max()), 1e-30)
+
+
 def _loader(name, bs, seed, flipped=False, paths=True):
     from i2vsgg_amd.model.utils import config as c
     from i2vsgg_amd.model.utils.net_utils import sampler
@@ -195,13 +201,16 @@ def test_sgg_padded_rows_have_no_effect(small_cfg):
         assert step.stage_batch(d)
         assert step.capture(warmup=1, restore=True), step.graph_error
         losses = [float(step()) for _ in range(3)]
-        out.append((losses, net.vrd.fc7.fc.weight.detach().cpu().numpy().copy(), net.vrd.fc_rel.fc.bias.detach().cpu().numpy().copy()))
+        out.append((losses, {n: p.detach().clone() for n, p in net.named_parameters() if n.startswith("vrd.")}))
         step.opt.unfuse()
-    (l0, w0, b0), (l1, w1, b1) = out
+        del step, net
+    (l0, w0), (l1, w1) = out
     assert l0[0] != l0[2]
     for a, b in zip(l0, l1):
         assert abs(a - b) <= 1e-5 * abs(a), (l0, l1)
-    assert _rel(w1, w0) < 1e-5 and _rel(b1, b0) < 1e-5
+    assert len(w0) == 26 and set(w0) == set(w1)
+    for n in w0:                                             # every tensor of the head, not fc7 and one bias
+        assert _rel_dev(w1[n], w0[n]) < 1e-5, n
 
 
 def test_instance_styled_captured_step_consumes_loader_batches_of_varying_size(small_cfg):
