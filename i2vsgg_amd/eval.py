@@ -7,6 +7,9 @@
                   eval branch of ``forward_relation`` returns; scaling by the box confidences, the ranking over the
                   (pair, predicate) grid and the top-k cut run on the device (``ops.relation_topk``).
 ``relation_frame``  backbone forward + ``forward_relation_eval`` + ``detection_output`` for one frame.
+``recognition_output``  lib/utils.py:570-582 -- the per-frame tail of predicate recognition on the ``vrd_data`` dict the eval
+                  branch of ``forward_predicate`` returns (numpy, the host form); ``ops.recognition_rows`` is its device form.
+``recognition_frame``  backbone forward + ``forward_predicate_eval`` + the device form of that tail for one frame.
 ``DetectStep``    ``detect_frame`` for several frames at a time as one replayable HIP graph (a branch per frame).
 ``RelationStep``  ``relation_frame`` + ``detection_output`` the same way.
 """
@@ -383,3 +386,61 @@ def relation_frame(net, im_data, im_info, im_path, k=100):
     fmap = net.RCNN_base(im_data)
     vrd_data = net.forward_relation_eval(fmap, im_info, im_path)
     return vrd_data, detection_output(vrd_data, k)
+
+
+# lib/utils.py:579 ``np.log(0.5*(rel_so_prior+1.0/15))``: the reference's literal (VidVRD's 15 object classes), not derived from
+# the class count of the run
+SO_PRIOR_SMOOTHING = 1.0 / 15
+
+
+def prior_log_table(so_prior, n_classes, n_rel):
+    """L (C-1, C-1, R) float64 = log(0.5 * (so_prior + 1/15)), computed once on the host by numpy (a device log may differ from
+    numpy's in the last bit, and the sum it enters is rounded to float32 afterwards).  Without a prior: log(1/30) everywhere."""
+    prior = (np.zeros((n_classes - 1, n_classes - 1, n_rel)) if so_prior is None
+             else np.asarray(so_prior, np.float64).reshape(n_classes - 1, n_classes - 1, n_rel))
+    return np.log(0.5 * (prior + SO_PRIOR_SMOOTHING))
+
+
+def _host_array(x):
+    return x.detach().cpu().numpy() if torch.is_tensor(x) else np.asarray(x)
+
+
+def recognition_output(vrd_data):
+    """lib/utils.py:570-582 on the record of ``forward_predicate_eval`` (device tensors are copied down).  Returns (sub_scores
+    (P,C), obj_scores (P,C), pre_scores (P,R) float32, tids) or four Nones when the frame has at most one box or no pair."""
+    if len(vrd_data["boxes"]) <= 1 or "rel_scores" not in vrd_data or len(vrd_data["tids"]) == 0:
+        return None, None, None, None
+    sub_scores = np.array(_host_array(vrd_data["sub_scores"]), np.float32)
+    sub_scores[:, 0] = 0.0
+    obj_scores = np.array(_host_array(vrd_data["obj_scores"]), np.float32)
+    obj_scores[:, 0] = 0.0
+    pre_scores = np.array(_host_array(vrd_data["rel_scores"]), np.float32)
+    pre_scores += np.log(0.5 * (np.asarray(vrd_data["rel_so_prior"], np.float64) + SO_PRIOR_SMOOTHING))   # float32(float64 sum)
+    return sub_scores, obj_scores, pre_scores, vrd_data["tids"]
+
+
+def recognition_rows_host(cls_prob, rel_prob, ixs, ixo, L):
+    """The numpy form of ``ops.recognition_rows`` (i2v_recognition_rows): the same values, bit for bit."""
+    prob = np.array(cls_prob, np.float32)
+    prob[:, 0] = 0.0
+    cls = prob.argmax(axis=1).astype(np.int32) if prob.shape[0] else np.zeros((0,), np.int32)
+    ixs, ixo = np.asarray(ixs, np.int64), np.asarray(ixo, np.int64)
+    pre = (np.asarray(rel_prob, np.float32).astype(np.float64) + np.asarray(L, np.float64)[cls[ixs] - 1, cls[ixo] - 1]).astype(np.float32)
+    return prob[ixs], prob[ixo], pre, cls
+
+
+@torch.no_grad()
+def recognition_frame(net, im_data, im_info, im_path):
+    """The per-frame work of the recognition branch of test_net_SGG_emb.py (:213-228): backbone, eval ``forward_predicate`` on
+    the frame's annotated pairs, ``recognition_output``'s tail on the device (``ops.recognition_rows``).  Returns what
+    ``recognition_output`` returns for the frame's record; only the final rows come down to the host."""
+    fmap = net.RCNN_base(im_data)
+    vrd_data, prob = net._predicate_eval(fmap, im_info, im_path)
+    if len(vrd_data["boxes"]) <= 1 or "rel_scores" not in vrd_data:
+        return None, None, None, None
+    rel = vrd_data["rel_scores"]
+    L = getattr(net.vrd, "_so_prior_log", None)
+    if L is None or L[0] is not net.vrd._so_prior:                # the table of this prior, computed once
+        L = net.vrd._so_prior_log = (net.vrd._so_prior, prior_log_table(net.vrd._so_prior, prob.shape[1], rel.shape[1]))
+    sub, obj, pre, _ = ops.recognition_rows(prob, rel, vrd_data["ixs"], vrd_data["ixo"], L[1])
+    return sub.cpu().numpy(), obj.cpu().numpy(), pre.cpu().numpy(), vrd_data["tids"]

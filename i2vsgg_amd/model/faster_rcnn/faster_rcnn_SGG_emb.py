@@ -51,6 +51,33 @@ def build_pair_tables(anno, im_scale, ih, iw, n_rel, margin=10):
     return gt, union, np.stack([bounds(sb), bounds(ob)], 1).astype(np.int32), labels, ixs, ixo
 
 
+def pair_track_ids(anno, im_path="?"):
+    """[subject_tid, object_tid] of every unique (s, o) pair of ``anno["rels"]`` in first-seen order (the order of
+    ``build_pair_tables``), from the first relation of the pair (:313-322).  ``anno["tids"]`` holds one [subject_tid,
+    object_tid] per relation, or one int per box; the type of its first entry tells which."""
+    rels, tids = anno["rels"], anno.get("tids")
+    if tids is None or len(tids) == 0:
+        raise ValueError("annotation of %s: %d relations and no tids" % (im_path, len(rels)))
+    first = tids[0]
+    if isinstance(first, (int, np.integer)):
+        if len(tids) != len(anno["boxes"]):
+            raise ValueError("annotation of %s: %d per-box tids for %d boxes" % (im_path, len(tids), len(anno["boxes"])))
+        of = lambda i, s, o: [int(tids[s]), int(tids[o])]
+    elif isinstance(first, (list, tuple, np.ndarray)) and len(first) == 2:
+        if len(tids) != len(rels):
+            raise ValueError("annotation of %s: %d per-relation tids for %d relations" % (im_path, len(tids), len(rels)))
+        of = lambda i, s, o: [int(tids[i][0]), int(tids[i][1])]
+    else:
+        raise ValueError("annotation of %s: tids are [subject_tid, object_tid] per relation or one int per box, got %r"
+                         % (im_path, first))
+    seen, out = set(), []
+    for i, (s, o, _) in enumerate(rels):
+        if (s, o) not in seen:
+            seen.add((s, o))
+            out.append(of(i, s, o))
+    return out
+
+
 def build_eval_pair_tables(boxes_scaled, ih, iw, margin=10):
     """Eval branch of forward_relation (:597-652): ALL ordered pairs i != j of the frame's boxes (i-major), their union
     boxes (+margin, clipped to (iw, ih)) and the integer bounds of the 32x32 dual masks.  float64 like the reference."""
@@ -163,11 +190,64 @@ class _fasterRCNN(nn.Module):
     def classify_boxes(self, base_feat, bboxes):
         """Box classification of the eval branch of forward_predicate (:278-291): ROIAlign -> ``_head_to_tail`` ->
         ``RCNN_cls_score`` -> softmax with the background column zeroed -> (classes, confs) per box."""
+        conf, cls = self.box_probabilities(base_feat, bboxes).max(1)
+        return cls.cpu().numpy(), conf.cpu().numpy()
+
+    @torch.no_grad()
+    def box_probabilities(self, base_feat, bboxes):
+        """The (n, n_classes) probability matrix behind ``classify_boxes`` (:285-289), background column zeroed, on the device."""
         pooled = self.RCNN_roi_align(base_feat, self._rois_of(bboxes, base_feat.device))
         prob = F.softmax(self.RCNN_cls_score(self._head_to_tail(pooled)), 1)
         prob[:, 0] = 0.0
-        conf, cls = prob.max(1)
-        return cls.cpu().numpy(), conf.cpu().numpy()
+        return prob
+
+    @torch.no_grad()
+    def forward_predicate_eval(self, fmap, im_info, im_path):
+        """Eval branch of forward_predicate (:278-379) for ONE frame, the per-frame stage of predicate recognition: the
+        annotated boxes of ``target_gt_rels[im_path]`` are classified (``box_probabilities``), the annotated (subject, object)
+        pairs -- unique, in first-seen order, each with the track ids of its first relation -- go through the relation head
+        in eval mode (softmax over predicates) -> the reference's ``vrd_data`` dict of this branch.  ``rel_scores``,
+        ``pre_feat``, ``sub_scores`` and ``obj_scores`` stay on the device; the feature map never visits the host.
+        ``anno["tids"]`` is one [subject_tid, object_tid] per relation (the reference's layout, :294, :322) or one int per box
+        (what ``seqnms.to_annotations`` writes).  A frame without relations gives the short record of :298-304; the
+        reference lets two or more boxes without relations fall into a zero-row head call, here that is the short record too."""
+        return self._predicate_eval(fmap, im_info, im_path)[0]
+
+    def _predicate_eval(self, fmap, im_info, im_path):
+        """-> (the record of ``forward_predicate_eval``, the probability matrix of its boxes on the device or None)."""
+        anno = self.vrd.target_gt_rels[im_path]
+        info = im_info.detach().cpu().numpy().reshape(-1, 3)
+        ih, iw, sc = float(info[0][0]), float(info[0][1]), float(info[0][2])
+        rels, n_box = anno["rels"], len(anno["boxes"])
+        pair_tids = pair_track_ids(anno, im_path) if len(rels) else []
+        if n_box == 0:
+            return {"boxes": [], "classes": [], "confs": []}, None
+        prob = self.box_probabilities(fmap[:1], np.array(anno["boxes"], np.float64).reshape(-1, 4) * sc)
+        host = prob.cpu().numpy()
+        classes = host.argmax(axis=-1)                   # the first index wins on equal values
+        confs = host[np.arange(n_box), classes]
+        if len(rels) < 1:
+            return {"boxes": anno["boxes"], "classes": classes, "confs": confs}, prob
+        gt, union, bnd, _, ixs, ixo = build_pair_tables(anno, sc, ih, iw, self.vrd.n_rel)
+        dev = fmap.device
+        so_prior = self.vrd._so_prior
+        rel_so_prior = (np.asarray(so_prior, np.float64)[classes[ixs] - 1, classes[ixo] - 1] if so_prior is not None
+                        else np.zeros((ixs.size, self.vrd.n_rel)))
+        b5 = np.zeros((gt.shape[0], 5), np.float32)
+        b5[:, 1:] = gt
+        r5 = np.zeros((union.shape[0], 5), np.float32)
+        r5[:, 1:] = union
+        was_training = self.vrd.training
+        self.vrd.eval()
+        try:
+            t_ixs, t_ixo = torch.from_numpy(ixs).to(dev), torch.from_numpy(ixo).to(dev)
+            rel_scores, pre_feat = self.vrd.forward_device(fmap[:1], torch.from_numpy(b5).to(dev), torch.from_numpy(r5).to(dev),
+                                                           rasterize_masks(bnd, dev), t_ixs, t_ixo)
+        finally:
+            self.vrd.train(was_training)
+        return {"ixs": ixs, "ixo": ixo, "boxes": anno["boxes"], "classes": classes, "confs": confs, "rel_so_prior": rel_so_prior,
+                "rel_scores": rel_scores, "sub_scores": prob[t_ixs], "obj_scores": prob[t_ixo], "pre_feat": pre_feat,
+                "tids": pair_tids}, prob
 
     def forward_predicate(self, fmap, im_info, im_path):
         paths = [im_path] if isinstance(im_path, str) else list(im_path)

@@ -1138,6 +1138,68 @@ def seq_nms(group_off, frame_no, box_off, box, score, link_iou=0.5, nms_iou=0.3,
     return tid, new_score, n_tracks
 
 
+def recognition_rows(cls_prob, rel_prob, ixs, ixo, L, device=None):
+    """The per-frame tail of predicate recognition in one launch (include/i2vsgg_hip.h, i2v_recognition_rows;
+    ``eval.recognition_rows_host`` is the numpy form).  cls_prob (B,C) fp32, rel_prob (P,R) fp32, ixs / ixo (P) int64, L
+    (C-1,C-1,R) fp64.  Returns device tensors (sub (P,C), obj (P,C), pre (P,R) fp32, cls (B) int32)."""
+    dev = torch.device(device if device is not None else (cls_prob.device if torch.is_tensor(cls_prob) else "cuda"))
+    if dev.type != "cuda":
+        raise _lib.I2VError("i2vsgg_amd ops run on the GPU only (got device %s); eval.recognition_rows_host is the host form" % dev)
+    cls_prob, rel_prob = _to_dev(cls_prob, torch.float32, dev), _to_dev(rel_prob, torch.float32, dev)
+    ixs, ixo, L = _to_dev(ixs, torch.int64, dev), _to_dev(ixo, torch.int64, dev), _to_dev(L, torch.float64, dev)
+    if cls_prob.dim() != 2 or rel_prob.dim() != 2:
+        raise ValueError("recognition_rows: cls_prob and rel_prob are matrices")
+    (B, C), (P, R) = cls_prob.shape, rel_prob.shape
+    if ixs.numel() != P or ixo.numel() != P or L.numel() != (C - 1) * (C - 1) * R:
+        raise ValueError("recognition_rows: array sizes do not agree")
+    sub = torch.zeros((P, C), device=dev)
+    obj = torch.zeros((P, C), device=dev)
+    pre = torch.zeros((P, R), device=dev)
+    cls = torch.zeros((B,), device=dev, dtype=torch.int32)
+    with torch.cuda.device(dev):
+        ws = launch.workspace(lib.i2v_recognition_rows_workspace_bytes(P), dev, "recognition_rows")
+        check(lib.i2v_recognition_rows(ptr(cls_prob), ptr(rel_prob), ptr(ixs), ptr(ixo), ptr(L), B, P, C, R, ptr(sub), ptr(obj),
+                                       ptr(pre), ptr(cls), ptr(ws), ws.numel(), stream()), "recognition_rows")
+        if P > 0:
+            _video_status(ws, "recognition_rows", "pair")
+    return sub, obj, pre, cls
+
+
+def recognition_align(rows, seg_off, seg_row, inst, n_classes, n_rel, device=None):
+    """Video-level alignment and accuracy@n of a packed batch of videos (include/i2vsgg_hip.h, i2v_recognition_align;
+    ``recognition.pack`` builds the arrays).  rows (N, 2C+R) fp64, seg_off (S+1), seg_row (M), inst (T,4) int32.  Returns
+    device tensors (mean (S,W) fp64, count (S) int32, top (S,3,10) int32, hit (T,7) int32, totals (8) int64, per_class
+    (C,2,2) int64)."""
+    dev = torch.device(device if device is not None else "cuda")
+    if dev.type != "cuda":
+        raise _lib.I2VError("i2vsgg_amd ops run on the GPU only (got device %s); recognition.align_arrays_host is the host form" % dev)
+    C, R = int(n_classes), int(n_rel)
+    W = 2 * C + R
+    rows = _to_dev(rows, torch.float64, dev)
+    seg_off, seg_row, inst = (_to_dev(x, torch.int32, dev) for x in (seg_off, seg_row, inst))
+    S, M, T = seg_off.numel() - 1, seg_row.numel(), inst.numel() // 4
+    if S < 0 or W <= 0 or rows.numel() % W or inst.numel() != 4 * T:
+        raise ValueError("recognition_align: array sizes do not agree")
+    N = rows.numel() // W
+    mean = torch.zeros((S, W), device=dev, dtype=torch.float64)
+    count = torch.zeros((S,), device=dev, dtype=torch.int32)
+    top = torch.full((S, 3, 10), -1, device=dev, dtype=torch.int32)
+    hit = torch.zeros((T, 7), device=dev, dtype=torch.int32)
+    totals = torch.zeros((8,), device=dev, dtype=torch.int64)
+    per_class = torch.zeros((max(C, 0), 2, 2), device=dev, dtype=torch.int64)
+    with torch.cuda.device(dev):
+        ws = launch.workspace(lib.i2v_recognition_align_workspace_bytes(S, T), dev, "recognition_align")
+        check(lib.i2v_recognition_align(ptr(rows), ptr(seg_off), ptr(seg_row), ptr(inst), N, M, S, T, C, R, ptr(mean), ptr(count),
+                                        ptr(top), ptr(hit), ptr(totals), ptr(per_class), ptr(ws), ws.numel(), stream()),
+              "recognition_align")
+        bad = ws[:8].view(torch.int32).tolist()                 # the caller reads the results next anyway
+        if bad[0]:
+            raise _lib.I2VError("recognition_align: the row table is out of range at segment %d" % (bad[0] - 1))
+        if bad[1]:
+            raise _lib.I2VError("recognition_align: segment or labels out of range at instance %d" % (bad[1] - 1))
+    return mean, count, top, hit, totals, per_class
+
+
 def _det_eval_device(device, what):
     dev = torch.device(device if device is not None else "cuda")
     if dev.type != "cuda":

@@ -453,3 +453,52 @@ def video_groundtruth(relations, seed):
         b = [[10.0 * k, 20.0, 90.0 + 10 * k, 120.0]] * 12
         gts.append({"triplet": [1, 61 - k, 2], "duration": [3, 15], "sub_traj": b, "obj_traj": b})
     return gts
+
+
+def recognition_set(seed, keys, sizes, frames_per_video, n_rel=62, n_classes=16, classes=None, n_tracks=4, n_relations=5):
+    """A small predicate-recognition set: every ``frames_per_video`` consecutive entries of ``keys`` (frame file names, in
+    order; ``sizes``: their (h, w)) are a video "0", "1", ... whose objects carry track ids that persist over its frames.
+    -> (target_gt_rels, groundtruth): per frame ``{"boxes", "box_classes", "rels": [[s, o, p]], "tids": [[subject_tid,
+    object_tid]] per relation}`` (the layout ``forward_predicate`` reads in eval mode, faster_rcnn_SGG_emb.py:277-322), and the
+    video-level ``{vid: [{"triplet": [s, p, o], "subject_tid", "object_tid", "duration": [start, end)}]}`` that matches them:
+    a relation is annotated in every frame of its duration in which both of its tracks are visible.  Subjects and objects are
+    named from ``classes`` when given (labels otherwise); predicates are labels."""
+    rng = np.random.default_rng(seed)
+    per = int(frames_per_video) if frames_per_video > 0 else max(len(keys), 1)
+    annos, gt = {}, {}
+    for v in range((len(keys) + per - 1) // per):
+        frames_v = list(range(v * per, min((v + 1) * per, len(keys))))
+        nf = len(frames_v)
+        cls = rng.integers(1, n_classes, n_tracks)
+        pos = rng.uniform(0.05, 0.55, (n_tracks, 2))                  # top-left corner and size as fractions of the frame
+        ext = rng.uniform(0.25, 0.4, (n_tracks, 2))
+        vel = rng.uniform(-0.01, 0.01, (n_tracks, 2))
+        visible = rng.random((nf, n_tracks)) < 0.85
+        visible[:, :2] = True                                         # two tracks in every frame
+        if nf > 2:
+            visible[nf // 2, 1:] = False                              # ... but for one frame with a single box
+        pairs = [(s, o) for s in range(n_tracks) for o in range(n_tracks) if s != o]
+        rels = []
+        for i in rng.permutation(len(pairs))[:n_relations]:
+            a = int(rng.integers(0, max(nf - 1, 1)))
+            rels.append((pairs[i][0], pairs[i][1], int(rng.integers(0, n_rel)), a, int(rng.integers(a + 1, nf + 1))))
+        rels.append(rels[0][:2] + ((rels[0][2] + 1) % n_rel,) + rels[0][3:])     # a second predicate on the first pair
+        seen = {}
+        for t, k in enumerate(frames_v):
+            h, w = sizes[k]
+            tracks = [j for j in rng.permutation(n_tracks) if visible[t, j]]
+            x1, y1 = (pos[tracks] + vel[tracks] * t).T
+            bx = np.floor(np.stack([x1 * w, y1 * h, np.minimum((x1 + ext[tracks, 0]) * w, w - 1),
+                                    np.minimum((y1 + ext[tracks, 1]) * h, h - 1)], 1))
+            slot = dict((j, i) for i, j in enumerate(tracks))
+            fr, ft = [], []
+            for r, (s, o, p, a, b) in enumerate(rels):
+                if a <= t < b and s in slot and o in slot:
+                    fr.append([slot[s], slot[o], p])
+                    ft.append([int(s), int(o)])
+                    seen.setdefault(r, []).append(t)
+            annos[keys[k]] = {"boxes": bx.tolist(), "box_classes": [int(cls[j]) for j in tracks], "rels": fr, "tids": ft}
+        name = (lambda c: classes[c]) if classes is not None else int
+        gt[str(v)] = [{"triplet": [name(int(cls[s])), p, name(int(cls[o]))], "subject_tid": int(s), "object_tid": int(o),
+                       "duration": [min(seen[r]), max(seen[r]) + 1]} for r, (s, o, p, a, b) in enumerate(rels) if r in seen]
+    return annos, gt

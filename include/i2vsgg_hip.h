@@ -271,6 +271,43 @@ int32_t i2v_seqnms(const int32_t* group_off, const int32_t* frame_no, const int3
                    double nms_iou, int32_t rescore, int32_t* tid, float* new_score, int32_t* n_tracks,
                    void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- Predicate recognition: the per-frame tail and the video-level alignment + accuracy@n --------------------------
+ * The pre_det branch of the reference's test loop (test_net_SGG_emb.py:213-228, 318-324): recognition_output
+ * (lib/utils.py:570-582) per frame, then alignment (:529-568, commented out there: it is the specification) and
+ * evaluate_recognition (:335-372) per video.  The rules are stated in full in i2vsgg_amd/recognition.py.
+ *
+ * i2v_recognition_rows, one wave per pair: cls_prob (n_boxes x n_classes fp32), rel_prob (n_pairs x n_rel fp32), ixs / ixo
+ * (n_pairs int64), L (n_classes-1 x n_classes-1 x n_rel fp64: log(0.5 * (so_prior + 1/15)), computed by the caller).
+ * cls (n_boxes) = arg-max of a box's row with column 0 read as zero, the lower index on ties; sub / obj (n_pairs x
+ * n_classes) = the rows of the pair's boxes with column 0 zero; pre (n_pairs x n_rel) = fp32(fp64(rel_prob) + L[cls[s]-1,
+ * cls[o]-1, :]) (an index of -1 wraps to the last row, as numpy's does).  Status word (first int32 of the workspace):
+ * 0, or 1 + the index of a pair whose ixs / ixo lies outside [0, n_boxes); nothing is written for such a pair.
+ *
+ * i2v_recognition_align, one wave per segment, then one thread per instance: rows (n_rows x W fp64, W = 2 * n_classes +
+ * n_rel, [sub | obj | pre]); seg_off (n_segments+1), seg_row (n_entries): segment s owns rows seg_row[seg_off[s] ..
+ * seg_off[s+1]), in ascending frame number; inst (n_instances x 4 int32): segment, subject, predicate and object label.
+ * mean (n_segments x W) = the fp64 sum of the segment's rows in seg_row order, one add per row, divided once by their
+ * number; count (n_segments); top (n_segments x 3 x 10): per column group the columns in descending order of the mean,
+ * the lower index first on equal values, unused slots -1; hit (n_instances x 7): sub@1 sub@5 obj@1 obj@5 pre@1 pre@5
+ * rel@1; totals (8 int64): the column sums of hit over instances of non-empty segments and their number; per_class
+ * (n_classes x 2 x 2 int64): for n in (1, 5) hits and total per class (subject hits under the subject's class plus object
+ * hits under the object's).  A segment without rows has count 0, mean 0, top -1; its instances have hit 0 and are left
+ * out of the counters.  The first two int32 of the workspace are status words: 1 + the index of a segment whose table
+ * entries are out of range (it comes out as an empty segment), and 1 + the index of an instance whose segment or labels
+ * are out of range (hit 0, not counted).  The means of one segment are ranked in LDS: W is at most
+ * I2V_RECOGNITION_MAX_WIDTH (16 KiB of doubles); a wider row is I2V_ERR_ARG.  i2v_recognition_rows has no such limit. */
+#define I2V_RECOGNITION_MAX_WIDTH 2048
+size_t  i2v_recognition_rows_workspace_bytes(int32_t n_pairs);
+int32_t i2v_recognition_rows(const float* cls_prob, const float* rel_prob, const int64_t* ixs, const int64_t* ixo,
+                             const double* L, int32_t n_boxes, int32_t n_pairs, int32_t n_classes, int32_t n_rel,
+                             float* sub, float* obj, float* pre, int32_t* cls, void* workspace, size_t workspace_bytes,
+                             void* stream);
+size_t  i2v_recognition_align_workspace_bytes(int32_t n_segments, int32_t n_instances);
+int32_t i2v_recognition_align(const double* rows, const int32_t* seg_off, const int32_t* seg_row, const int32_t* inst,
+                              int32_t n_rows, int32_t n_entries, int32_t n_segments, int32_t n_instances,
+                              int32_t n_classes, int32_t n_rel, double* mean, int32_t* count, int32_t* top, int32_t* hit,
+                              int64_t* totals, int64_t* per_class, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- VOC detection evaluation that ends the detector test loop (lib/datasets/voc_eval.py:132-212) ----------------
  * Detections lie in results-file order (class, then image, then row; i2vsgg_amd/detection_eval.py pack()): det_key
  * (n_det int32) is the score as the results file would hold it ('%.3f'), in thousandths; det_box (n_det x 4 fp64) the

@@ -1158,13 +1158,49 @@ def gen_det_eval():
          gt_hard=np.concatenate([e["gt_ishard"] for e in roidb]).astype(np.int32), npos=pk.npos, **out)
 
 
+# ----------------------------------------------------------------------------- predicate recognition
+def gen_recognition():
+    """tests/golden/recognition.npz: the reference's recognition_output (lib/utils.py:570-582) on one seeded frame record and
+    its evaluate_recognition (:335-372) on ``recognition.video_recognitions`` of the seeded case set of
+    tests/recognition_cases.py (the reference's alignment, which was to produce those records, is commented out).  The file
+    holds data only: the four outputs, the seven returned numbers and the per-class values parsed from the printed lines."""
+    import copy
+    import re
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import recognition_cases as cases
+    from i2vsgg_amd import recognition
+    ns = _utils_functions(["recognition_output", "evaluate_recognition"])
+    rec = cases.frame_record()
+    data = copy.deepcopy(rec)
+    data["rel_scores"] = torch.from_numpy(data["rel_scores"])
+    sub, obj, pre, tids = ns["recognition_output"](data)
+    cs = cases.golden_set()
+    assert cs["redraws"] == 0, cs["redraws"]
+    pk = recognition.pack(cs["frame_recognitions"], cs["groundtruth"], cs["classes"], cs["predicates"])
+    mean = recognition.align_arrays_host(pk)[0]
+    lines = []
+    ns["print"] = lambda *a, **k: lines.append(" ".join(str(x) for x in a))
+    acc = ns["evaluate_recognition"](recognition.video_recognitions(pk, mean))
+    per_class = np.full((2, 16), np.nan)
+    for line in lines:
+        m = re.match(r"object #(\d+) acc@(\d+) : (.*)$", line)
+        if m:
+            per_class[(1, 5).index(int(m.group(2))), int(m.group(1))] = float(m.group(3))
+    seven = np.array([acc["sub"][1], acc["sub"][5], acc["obj"][1], acc["obj"][5], acc["pre"][1], acc["pre"][5], acc["rel"][1]],
+                     np.float64)
+    print("  recognition: %d segments, %d instances, %d aligned; sub@1 %.4f obj@1 %.4f pre@1 %.4f pre@5 %.4f rel@1 %.4f" % (
+        len(pk.segments), len(pk.inst), sum(len(v) for v in recognition.video_recognitions(pk, mean).values()), *seven[[0, 2, 4, 5, 6]]))
+    save("recognition", "extracted", sub_scores=sub, obj_scores=obj, pre_scores=pre, tids=np.asarray(tids, np.int64), metrics=seven,
+         per_class=per_class, n_segments=np.array(len(pk.segments)), n_instances=np.array(len(pk.inst)))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--only", default="")
     a = ap.parse_args()
     os.makedirs(GOLD, exist_ok=True)
     todo = a.only.split(",") if a.only else ["direct", "roialign", "roialign_fresh", "tails", "rpn", "nets", "full", "ctx", "step",
-                                             "vrd", "video", "det_eval"]
+                                             "vrd", "video", "det_eval", "recognition"]
     if "direct" in todo:
         print("[direct imports]")
         gen_direct()
@@ -1189,6 +1225,9 @@ def main():
     if "video" in todo or "video_edges" in todo:
         print("[video evaluation on the edge set: the same lib/utils.py functions]")
         gen_video_edges()
+    if "recognition" in todo:
+        print("[predicate recognition: recognition_output / evaluate_recognition of lib/utils.py compiled from their own lines]")
+        gen_recognition()
     if any(t in todo for t in ("rpn", "nets", "full", "vrd", "ctx", "step")):
         print("[imports with placeholders]")
         cfg = install_placeholders()
