@@ -1,7 +1,8 @@
-"""``_fasterRCNN`` of the SGG_emb stage (faster_rcnn/faster_rcnn_SGG_emb.py:32-379), pre_det task.
+"""``_fasterRCNN`` of the SGG_emb stage (faster_rcnn/faster_rcnn_SGG_emb.py:32-379), pre_det and rel_det tasks.
 
 forward(im_data, im_info, gt_boxes, num_boxes, im_path, target=False)
-  training -> BCE-with-logits loss of the relation head on the annotated (subject, object) pairs.
+  training -> BCE-with-logits loss of the relation head on the annotated (subject, object) pairs (pre_det), or on pairs of
+  detected boxes sampled around them (rel_det, ``forward_relation_train``).
 The reference moves the backbone output to the host, builds pairs / union boxes / masks in Python
 loops and uploads the map again, one frame per step whatever ``--bs`` says.  Here the feature map never
 leaves the GPU, ``im_path`` may be a list (one entry per frame; loss = mean over frames, i.e. the
@@ -123,8 +124,10 @@ class _fasterRCNN(nn.Module):
         with torch.no_grad():                            # base_feat.detach() of the reference (:148)
             base_feat = self.RCNN_base(im_data)
         task = getattr(self.args, "vrd_task", "pre_det")
-        if task != "pre_det":
-            raise NotImplementedError("vrd_task=%r: only pre_det is live in the reference (SURVEY.md A10)" % task)
+        if task not in ("pre_det", "rel_det"):
+            raise NotImplementedError("vrd_task=%r: the reference has pre_det and rel_det (SURVEY.md A10)" % task)
+        if self.training and task == "rel_det":
+            return self.forward_relation_train(base_feat, im_info, im_path)
         if not self.training:
             # eval forward_predicate is broken in the reference; the live eval path is the
             # relation branch on the target annotations (forward_relation :583-697)
@@ -287,6 +290,36 @@ class _fasterRCNN(nn.Module):
         w = torch.cat([torch.full((c,), 1.0 / (c * len(counts))) for c in counts]).to(dev)
         from i2vsgg_amd import ops
         return ops.bce_rows(score, target, w)
+
+    def forward_relation_train(self, fmap, im_info, im_path):
+        """Training branch of forward_relation (:476-578), the rel_det task: the relation head on DETECTED boxes.  Annotations
+        come from ``vrd.source_gt_rels``, detections from ``vrd.source_det_boxes`` (same keys; "boxes" in unscaled pixels,
+        "box_classes", "scores": what ``seqnms.to_annotations`` writes).  The rules are ``i2vsgg_amd.relation_targets``'; the
+        reference's branch does not run as shipped.  The host packs and uploads the tables, the padded
+        (F*B, 5) box table and the uniforms (one draw from numpy's global stream); matching, sampling, merging, union boxes and
+        mask bounds run in ``ops.relation_targets``, and from the upload to the loss nothing is read back: every shape is fixed
+        (B = 64 box rows and P = 64 pair rows per frame, padding rows carry weight 0).  Returns the loss, the mean over the
+        frames of the per-frame BCE mean (a frame without a pair contributes 0, :489,:494,:516); ``rel_det_n_pairs``,
+        ``rel_det_n_dropped`` (F) and ``rel_det_status`` (the kernels' status word) stay on the device as attributes."""
+        from i2vsgg_amd import ops, relation_targets
+        if self.vrd.spatial_type == 1:
+            raise ValueError("vrd_task=rel_det builds the dual masks of its sampled pairs on the device; the relative-location "
+                             "feature (--spatial_type 1) is a host loop over known pairs and runs under pre_det only")
+        paths = [im_path] if isinstance(im_path, str) else list(im_path)
+        if len(paths) == 1 and fmap.size(0) > 1:
+            fmap = fmap[:1]
+        for path in paths:
+            if path not in self.vrd.source_det_boxes:
+                raise KeyError("vrd_task=rel_det: no detections for %r in vrd.source_det_boxes (--source_det_boxes_path)" % (path,))
+        info = im_info.detach().cpu().numpy().reshape(-1, 3)[:len(paths)]
+        pk = relation_targets.pack([self.vrd.source_det_boxes[q] for q in paths], [self.vrd.source_gt_rels[q] for q in paths],
+                                   info, self.vrd.n_rel, names=paths)
+        dev = fmap.device
+        tg = ops.relation_targets(*pk.tables(), n_rel=self.vrd.n_rel, device=dev, read_status=False)
+        boxes = torch.from_numpy(pk.boxes5).to(dev)
+        score, _ = self.vrd.forward_device(fmap, boxes, tg["rel5"], rasterize_masks(tg["bounds"], dev), tg["ixs"], tg["ixo"])
+        self.rel_det_n_pairs, self.rel_det_n_dropped, self.rel_det_status = tg["n_pairs"], tg["n_dropped"], tg["status"]
+        return ops.bce_rows(score, tg["labels"], tg["w"])
 
     def _init_weights(self):
         def normal_init(m, mean, std):

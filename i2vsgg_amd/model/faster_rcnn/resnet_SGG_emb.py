@@ -44,6 +44,9 @@ class vrd(nn.Module):
         self.obj_vecs, self.prd_vecs = all_obj_vecs, all_prd_vecs
         self._so_prior = None
         self.source_gt_rels, self.target_gt_rels = {}, {}
+        self.source_det_boxes = {}       # rel_det: detections per frame (boxes in unscaled pixels, box_classes, scores)
+        if getattr(args, "source_det_boxes_path", None):
+            self.source_det_boxes = _load_pickle(args.source_det_boxes_path)
         if getattr(args, "source_so_prior_path", None):
             self._so_prior = np.array(_load_pickle(args.source_so_prior_path))
         if getattr(args, "source_gt_rels_path", None):

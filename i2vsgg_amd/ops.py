@@ -1138,6 +1138,44 @@ def seq_nms(group_off, frame_no, box_off, box, score, link_iou=0.5, nms_iou=0.3,
     return tid, new_score, n_tracks
 
 
+def relation_targets(det_off, det_box, det_cls, gt_off, gt_box, gt_cls, rel_off, rel, u, ih, iw, n_rel, device=None, read_status=True):
+    """The rel_det targets of a minibatch in two launches (include/i2vsgg_hip.h, i2v_relation_targets; the rules and the
+    tables: ``i2vsgg_amd.relation_targets``, whose ``pack`` builds them).  Arrays or tensors; ``u`` (N_r, 10) uint32 (a tensor:
+    its int32 view).  Returns a dict of device tensors: rel5 (F*64, 5) fp32, bounds (F*64, 2, 4) int32, labels (F*64, n_rel)
+    fp32, ixs / ixo (F*64) int64, w (F*64) fp32, n_pairs / n_dropped (F) int32, samp (N_r, 10, 2) int32 and ``status`` (the
+    int32 status word).  ``read_status=False`` leaves the status word on the device: nothing is read back, the call only enqueues."""
+    dev = torch.device(device if device is not None else "cuda")
+    if dev.type != "cuda":
+        raise _lib.I2VError("i2vsgg_amd ops run on the GPU only (got device %s); relation_targets.relation_targets_host is the host form" % dev)
+    if isinstance(u, np.ndarray):
+        u = np.ascontiguousarray(u, np.uint32).view(np.int32)
+    elif torch.is_tensor(u) and u.dtype != torch.int32:
+        u = u.view(torch.int32)
+    det_off, gt_off, rel_off, det_cls, gt_cls, rel, u = (_to_dev(x, torch.int32, dev) for x in (det_off, gt_off, rel_off, det_cls, gt_cls, rel, u))
+    det_box, gt_box, ih, iw = (_to_dev(x, torch.float64, dev) for x in (det_box, gt_box, ih, iw))
+    F, ND, NG, NR, n_rel = ih.numel(), det_cls.numel(), gt_cls.numel(), rel.numel() // 3, int(n_rel)
+    if (iw.numel() != F or det_off.numel() != F + 1 or gt_off.numel() != F + 1 or rel_off.numel() != F + 1 or det_box.numel() != 4 * ND
+            or gt_box.numel() != 4 * NG or rel.numel() != 3 * NR or u.numel() != 10 * NR or n_rel < 0):
+        raise ValueError("relation_targets: array sizes do not agree")
+    rows = F * 64
+    out = {"rel5": torch.empty((rows, 5), device=dev), "bounds": torch.empty((rows, 2, 4), device=dev, dtype=torch.int32),
+           "labels": torch.empty((rows, n_rel), device=dev), "ixs": torch.empty((rows,), device=dev, dtype=torch.int64),
+           "ixo": torch.empty((rows,), device=dev, dtype=torch.int64), "w": torch.empty((rows,), device=dev),
+           "n_pairs": torch.empty((F,), device=dev, dtype=torch.int32), "n_dropped": torch.empty((F,), device=dev, dtype=torch.int32),
+           "samp": torch.empty((NR, 10, 2), device=dev, dtype=torch.int32)}
+    with torch.cuda.device(dev):
+        # the status word is part of the result: its own buffer, not the shared workspace the next op overwrites
+        ws = torch.zeros((lib.i2v_relation_targets_workspace_bytes(F),), device=dev, dtype=torch.uint8)
+        check(lib.i2v_relation_targets(ptr(det_off), ptr(det_box), ptr(det_cls), ptr(gt_off), ptr(gt_box), ptr(gt_cls), ptr(rel_off),
+                                            ptr(rel), ptr(u), ptr(ih), ptr(iw), F, ND, NG, NR, n_rel, ptr(out["rel5"]), ptr(out["bounds"]),
+                                            ptr(out["labels"]), ptr(out["ixs"]), ptr(out["ixo"]), ptr(out["w"]), ptr(out["n_pairs"]),
+                                            ptr(out["n_dropped"]), ptr(out["samp"]), ptr(ws), ws.numel(), stream()), "relation_targets")
+        if read_status and F > 0:
+            _video_status(ws, "relation_targets", "frame")
+    out["status"] = ws[:4].view(torch.int32)[0]
+    return out
+
+
 def recognition_rows(cls_prob, rel_prob, ixs, ixo, L, device=None):
     """The per-frame tail of predicate recognition in one launch (include/i2vsgg_hip.h, i2v_recognition_rows;
     ``eval.recognition_rows_host`` is the numpy form).  cls_prob (B,C) fp32, rel_prob (P,R) fp32, ixs / ixo (P) int64, L

@@ -228,6 +228,34 @@ def relation_annotation(seed, n_boxes=32, n_pairs=32, n_rel=62, n_classes=16, im
             "rels": [rels[i] for i in order]}
 
 
+def detections_for(seed, anno, exact=False, jitter=0.08, copies=1, n_wrong=2, n_distractors=4, n_classes=16, im_h=600, im_w=1000):
+    """Detections for one annotated frame, in the layout ``seqnms.to_annotations`` writes and ``vrd.source_det_boxes`` holds:
+    {"boxes" (unscaled pixels), "box_classes", "scores"}.  ``exact``: the annotated boxes themselves, in their order, score 1.
+    Otherwise ``copies`` times every annotated box with each corner coordinate moved by at most ``jitter`` of that side (so its overlap with
+    the annotated box is at least ((1 - 2 jitter) / (1 + 2 jitter))^2: 0.52 at the default, a match; above 0.17 some fall
+    below 0.5), ``n_wrong`` copies of annotated boxes under another class and ``n_distractors`` boxes anywhere, all clipped
+    to the image, in a seeded order, scores in (0.7, 1)."""
+    gt = np.asarray(anno["boxes"], np.float64).reshape(-1, 4)
+    cls = [int(c) for c in anno["box_classes"]]
+    if exact:
+        return {"boxes": gt.tolist(), "box_classes": cls, "scores": [1.0] * len(cls)}
+    rng = np.random.default_rng(seed + 4241)
+    side = np.stack([gt[:, 2] - gt[:, 0], gt[:, 3] - gt[:, 1]] * 2, 1)
+    out = [gt + rng.uniform(-jitter, jitter, gt.shape) * side for _ in range(copies)]
+    out_cls = list(cls) * copies
+    if len(gt) and n_wrong:
+        pick = rng.integers(0, len(gt), n_wrong)
+        out.append(gt[pick] + rng.uniform(-jitter, jitter, (n_wrong, 4)) * side[pick])
+        out_cls += [cls[i] % (n_classes - 1) + 1 for i in pick]
+    if n_distractors:
+        out.append(boxes(seed + 4242, n_distractors, im_h, im_w).astype(np.float64))
+        out_cls += [int(c) for c in rng.integers(1, n_classes, n_distractors)]
+    b = np.clip(np.concatenate(out), 0, [im_w - 1, im_h - 1, im_w - 1, im_h - 1])
+    order = rng.permutation(len(b))
+    scores = rng.uniform(0.7, 1.0, len(b))
+    return {"boxes": b[order].tolist(), "box_classes": [out_cls[i] for i in order], "scores": scores.tolist()}
+
+
 def word_vectors(seed, n, dim=300):
     """Stand-in for the GloVe rows (``all_obj_vecs`` / ``all_prd_vecs``): (n,dim) fp32."""
     return np.random.default_rng(seed).standard_normal((n, dim), dtype=np.float32)

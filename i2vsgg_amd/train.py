@@ -1192,14 +1192,15 @@ def _randomise_bn(net, seed):
             m.invalidate()
 
 
-def build_sgg_net(layers=101, n_rel=62, n_cls=16, seed=0, device="cuda:0", emb_dim=300, use_obj_visual=True, spatial_type=2):
+def build_sgg_net(layers=101, n_rel=62, n_cls=16, seed=0, device="cuda:0", emb_dim=300, use_obj_visual=True, spatial_type=2,
+                  vrd_task="pre_det"):
     """Random-init SGG_emb model of the reference architecture (no checkpoint is reachable).  ``emb_dim``,
-    ``use_obj_visual``, ``spatial_type``: the reference's flags (parser_func.py:155-163,182)."""
+    ``use_obj_visual``, ``spatial_type``, ``vrd_task``: the reference's flags (parser_func.py:155-163,182)."""
     import argparse
     from .model.faster_rcnn.resnet_SGG_emb import resnet
     torch.manual_seed(seed)
     args = argparse.Namespace(num_relations=n_rel, num_classes=n_cls, emb_dim=int(emb_dim), use_obj_visual=bool(use_obj_visual),
-                              spatial_type=int(spatial_type), vrd_task="pre_det")
+                              spatial_type=int(spatial_type), vrd_task=vrd_task)
     net = resnet(tuple(range(n_cls)), args, layers, obj_vecs=syn.word_vectors(22, n_cls),
                  prd_vecs=syn.word_vectors(21, n_rel))
     net.create_architecture()

@@ -271,6 +271,36 @@ int32_t i2v_seqnms(const int32_t* group_off, const int32_t* frame_no, const int3
                    double nms_iou, int32_t rescore, int32_t* tid, float* new_score, int32_t* n_tracks,
                    void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- rel_det training targets: relation-head rows from detected boxes (faster_rcnn_SGG_emb.py:476-578) -------------
+ * The reference's branch does not run as shipped; what it means to compute is restated, with the exact rules, in
+ * i2vsgg_amd/relation_targets.py.  Packed tables of a minibatch of n_frames frames:
+ *   det_off (n_frames+1), det_box (n_det x 4 fp64, network-input pixels), det_cls (n_det): frame f owns detections
+ *   [det_off[f], det_off[f+1]), at most 64;  gt_off, gt_box (n_gt x 4 fp64), gt_cls: its annotated boxes;  rel_off, rel
+ *   (n_relations x 3: subject box, object box -- local to the frame -- and predicate);  u (n_relations x 10 uint32): the
+ *   uniforms of the draws;  ih, iw (n_frames fp64).
+ * Detection a matches annotated box g when the classes are equal and the +1-convention overlap is >= 0.5.  The candidates
+ * of a relation are the (a, b), a != b, with a matching its subject box and b its object box, a-major; a candidate's weight
+ * is floor(overlap_a * overlap_b * 65536).  Draw k of min(10, candidates): t = (u * sum of the weights alive) >> 32, the
+ * first alive candidate whose running sum exceeds t is drawn and leaves (relation_sample_kernel: one wave per relation, lane a
+ * is detection a). The entries (relation, draw) of a frame merge by (a, b) in first-seen order into at most 64 rows
+ * (relation_emit, one workgroup per frame), every row beyond being counted in n_dropped.
+ * Outputs, 64 rows per frame, all written (padding: ixs = ixo = 64 f, zero box, bounds, labels and weight):
+ *   rel5 (64 n_frames x 5 fp32: frame, union box + 10 clipped to the image), bounds (x 2 x 4 int32: the 32 x 32 dual-mask
+ *   bounds of subject and object), labels (x n_pred fp32 multi-hot), ixs / ixo (int64 rows 64 f + a of the padded box
+ *   table), w (fp32(1 / (n_pairs[f] * n_frames))), n_pairs / n_dropped (n_frames), samp (n_relations x 10 x 2 int32: the
+ *   draws, -1 where there is none).
+ * The first int32 of the workspace is a status word: 0, or 1 + the index of a frame whose table entries were out of range
+ * (offsets not monotone or outside the arrays, more than 64 detections, a relation outside the frame's boxes or predicates,
+ * an image size that is not positive and finite); such a frame comes out as padding rows only, without draws. */
+size_t  i2v_relation_targets_workspace_bytes(int32_t n_frames);
+int32_t i2v_relation_targets(const int32_t* det_off, const double* det_box, const int32_t* det_cls,
+                             const int32_t* gt_off, const double* gt_box, const int32_t* gt_cls,
+                             const int32_t* rel_off, const int32_t* rel, const uint32_t* u, const double* ih,
+                             const double* iw, int32_t n_frames, int32_t n_det, int32_t n_gt, int32_t n_relations,
+                             int32_t n_pred, float* rel5, int32_t* bounds, float* labels, int64_t* ixs, int64_t* ixo,
+                             float* w, int32_t* n_pairs, int32_t* n_dropped, int32_t* samp,
+                             void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- Predicate recognition: the per-frame tail and the video-level alignment + accuracy@n --------------------------
  * The pre_det branch of the reference's test loop (test_net_SGG_emb.py:213-228, 318-324): recognition_output
  * (lib/utils.py:570-582) per frame, then alignment (:529-568, commented out there: it is the specification) and

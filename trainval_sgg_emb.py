@@ -43,7 +43,10 @@ def parse_args(argv=None):
                         "filter-gradient kernels")
     p.add_argument("--num_classes", type=int, default=16)
     p.add_argument("--num_relations", type=int, default=62)
-    p.add_argument("--vrd_task", default="pre_det")
+    p.add_argument("--vrd_task", default="pre_det",
+                   help="pre_det: the relation head on the annotated boxes (the captured step).  rel_det: on detected boxes "
+                        "(--source_det_boxes_path) matched to the annotated ones, pairs sampled per annotated relation "
+                        "(i2vsgg_amd/relation_targets.py), on the eager loop")
     # parser_func.py:155-163,182.  The reference declares the first two ``type=bool`` (any value given on its command line
     # parses to True, i.e. spatial_type 1: SURVEY.md A15); here they are integers and select what they name.  The defaults
     # (1, 2, 300) are what every reference script runs and what the captured step packs; the other variants of the relation
@@ -53,6 +56,9 @@ def parse_args(argv=None):
     p.add_argument("--emb_dim", type=int, default=300, help="dimension of the embedding space (the word vectors' dimension)")
     p.add_argument("--adaptation", default="adap")
     p.add_argument("--source_gt_rels_path", default="")
+    p.add_argument("--source_det_boxes_path", default="",
+                   help="rel_det: pickle {frame file name: {'boxes' (unscaled pixels), 'box_classes', 'scores'}}, the layout of "
+                        "track_detections.py's tracked_boxes.pkl; 'synthetic': seeded detections around the annotated boxes")
     p.add_argument("--cuda", action="store_true", default=True)
     p.add_argument("--disp_interval", type=int, default=5)
     p.add_argument("--scale", type=int, default=0, help="shorter image side (cfg.TRAIN.SCALES; 0: the yml's 600)")
@@ -78,6 +84,35 @@ def parse_args(argv=None):
     p.add_argument("--no-graph", action="store_true", help="eager launches instead of the captured step")
     p.add_argument("--set", dest="set_cfgs", nargs=argparse.REMAINDER, default=None)
     return p.parse_args(argv)
+
+
+def check_task_args(a):
+    """What --vrd_task needs, before anything is built."""
+    if a.vrd_task not in ("pre_det", "rel_det"):
+        raise SystemExit("--vrd_task %s: the tasks are pre_det and rel_det" % a.vrd_task)
+    if a.vrd_task == "rel_det":
+        if not a.source_det_boxes_path:
+            raise SystemExit("--vrd_task rel_det trains on detected boxes: pass --source_det_boxes_path <tracked_boxes.pkl> "
+                             "(or 'synthetic')")
+        if a.spatial_type == 1:
+            raise SystemExit("--vrd_task rel_det builds dual masks on the device: --spatial_type 0 or 2")
+        if a.device_prep or a.resume_train:
+            raise SystemExit("--vrd_task rel_det runs the plain eager loop: no --device_prep, --resume_train")
+
+
+def load_det_boxes(a, gt_rels):
+    """The detections of --source_det_boxes_path, checked against the annotations' frames."""
+    if a.source_det_boxes_path == "synthetic":
+        from i2vsgg_amd import synthetic as syn
+        return {k: syn.detections_for(i, an, n_classes=a.num_classes) for i, (k, an) in enumerate(gt_rels.items())}
+    import pickle
+    with open(a.source_det_boxes_path, "rb") as f:
+        dets = pickle.load(f, encoding="bytes")
+    missing = [k for k in gt_rels if k not in dets]
+    if missing:
+        raise SystemExit("--source_det_boxes_path %s has no entry for %d annotated frames (first: %s)" % (
+            a.source_det_boxes_path, len(missing), missing[0]))
+    return dets
 
 
 def checkpoint_name(a, session, epoch, step):
@@ -163,6 +198,7 @@ def init_from_detector(path, net, log=print):
 
 def main(argv=None):
     a = parse_args(argv)
+    check_task_args(a)
     from i2vsgg_amd import parallel, train
     from i2vsgg_amd.model.utils import config as c
     from i2vsgg_amd.model.utils.net_utils import sampler
@@ -193,7 +229,7 @@ def main(argv=None):
     iters_per_epoch = a.iters_per_epoch or (train_size // a.batch_size // world)
 
     net = train.build_sgg_net(101 if a.net == "res101" else 50, a.num_relations, a.num_classes, device=dev, emb_dim=a.emb_dim,
-                              use_obj_visual=a.use_obj_visual, spatial_type=a.spatial_type)
+                              use_obj_visual=a.use_obj_visual, spatial_type=a.spatial_type, vrd_task=a.vrd_task)
     if a.source_gt_rels_path:
         import pickle
         with open(a.source_gt_rels_path, "rb") as f:
@@ -206,7 +242,9 @@ def main(argv=None):
         # resnet_SGG_emb.py:86,97: so_vis_embeddings is FC(4096, emb_dim) but fc_so is FC(300*2, 256) -- the reference's own
         # head only composes at emb_dim 300 while the visual embeddings are on (kept: checkpoints carry that shape)
         raise SystemExit("--emb_dim %d needs --use_obj_visual 0: fc_so is FC(300*2, 256) in the reference (resnet_SGG_emb.py:97)" % a.emb_dim)
-    if not (a.use_obj_visual == 1 and a.spatial_type == 2):
+    if a.vrd_task == "rel_det":
+        net.vrd.source_det_boxes = load_det_boxes(a, net.vrd.source_gt_rels)
+    if a.vrd_task == "rel_det" or not (a.use_obj_visual == 1 and a.spatial_type == 2):
         return train_variant(a, net, dataloader_s, iters_per_epoch, dev, rank, world)
     step = train.SGGEmbStep(net, a.batch_size, vrd_lr=a.vrd_lr, device=dev, use_graph=not a.no_graph and dev.type == "cuda",
                             stage_synthetic=False, optimizer=a.optimizer)
@@ -299,11 +337,21 @@ def main(argv=None):
 def train_variant(a, net, loader, iters_per_epoch, dev, rank, world):
     """The non-default variants of the relation head (--use_obj_visual 0, --spatial_type 0 / 1): the reference's loop as written
     (trainval_net_SGG_emb.py:204-255) -- forward of the model on the minibatch, backward, optimizer step -- on eager launches of
-    the same kernels (the captured step packs the default head's inputs only)."""
+    the same kernels (the captured step packs the default head's inputs only).  --vrd_task rel_det runs here too: its forward
+    samples its pairs on the device (``forward_relation_train``); stage 2 starts from a detector checkpoint, so --r is allowed."""
     from i2vsgg_amd import parallel, train
-    if a.device_prep or a.resume or a.resume_train:
+    rel_det = a.vrd_task == "rel_det"
+    if a.device_prep or a.resume_train or (a.resume and not rel_det):
         raise SystemExit("--use_obj_visual 0 / --spatial_type 0|1 run the plain eager loop: no --device_prep, --r, --resume_train")
+    if a.resume:                                             # the reference's --r: detector weights in, vrd.* untouched
+        if not a.load_name:
+            raise SystemExit("--r needs --load_name <detector checkpoint> (trainval_net_SGG_emb.py:156)")
+        loaded, missing = init_from_detector(a.load_name, net, log=print if rank == 0 else (lambda *_: None))
+        if rank == 0:
+            print("loaded checkpoint %s (%d detector tensors, %d not in the file)" % (a.load_name, len(loaded), len(missing)))
     opt = train.make_optimizer(a.optimizer, [(n, p) for n, p in net.named_parameters() if n.startswith("vrd.")], a.vrd_lr)
+    if a.resume:
+        opt.bump()                                           # filters changed under every cache derived from them
     it_data = iter(loader)
     for epoch in range(a.start_epoch, a.max_epochs + 1):
         if epoch > 1 and (epoch - 1) % a.lr_decay_step == 0:
@@ -323,6 +371,12 @@ def train_variant(a, net, loader, iters_per_epoch, dev, rank, world):
                 loss = net(im, info, gt, nb, paths)
                 if not torch.is_tensor(loss):                               # no annotated relation in the minibatch (:177-183)
                     loss = None
+                elif rel_det:
+                    # the step's one read: the loss and, with it, the number of sampled pairs.  A minibatch without a pair
+                    # (no detection matches, :489,:494,:516) is skipped like one without annotated relations
+                    loss_value, n_pairs = torch.stack((loss.detach().double(), net.rel_det_n_pairs.sum().double())).tolist()
+                    if n_pairs == 0:
+                        loss = None
             # The reference's `continue` is a single-process one.  With several ranks the exchange is a collective: a rank
             # without a loss still brings (zero) gradients, and the step is skipped only when NO rank has one -- every rank
             # learns that from the same all-reduced count, so all of them take the same branch (round-5 advice)
@@ -335,11 +389,11 @@ def train_variant(a, net, loader, iters_per_epoch, dev, rank, world):
             opt.step()
             if loss is None:
                 continue
-            acc, n_acc = acc + float(loss.detach()), n_acc + 1
+            acc, n_acc = acc + (loss_value if rel_det else float(loss.detach())), n_acc + 1
             if (it + 1) % a.disp_interval == 0 and rank == 0 and n_acc:
-                print("[session %d][epoch %2d][iter %4d/%4d] loss: %.4f, vrd_lr: %.2e, %.1f frames/s (eager, variant head)" % (
+                print("[session %d][epoch %2d][iter %4d/%4d] loss: %.4f, vrd_lr: %.2e, %.1f frames/s (eager, %s)" % (
                     a.session, epoch, it + 1, iters_per_epoch, acc / n_acc, opt.lr_of("vrd.fc7.fc.weight"),
-                    world * a.batch_size * a.disp_interval / (time.time() - t0)))
+                    world * a.batch_size * a.disp_interval / (time.time() - t0), "rel_det" if rel_det else "variant head"))
                 t0, acc, n_acc = time.time(), 0.0, 0
         if not a.no_save:
             path = save_checkpoint(a, net, opt, epoch, iters_per_epoch - 1, rank)
