@@ -161,8 +161,7 @@ __device__ inline float dp_img_load(const float* img, int row, int col) {
 
 __global__ void __launch_bounds__(DP_THREADS)
 dpixel_fwd_kernel(const float* __restrict__ x, const float* __restrict__ w1, const float* __restrict__ w2,
-                  const float* __restrict__ w3, float* __restrict__ h1, float* __restrict__ h2, float* __restrict__ d,
-                  float* __restrict__ feat, int M, int pix_per_roi) {
+                  const float* __restrict__ w3, float* __restrict__ h1, float* __restrict__ h2, float* __restrict__ d, int M) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     float* stA = lds;
     float* stB = stA + 2 * DP_ROWS * DP_BK;
@@ -190,13 +189,19 @@ dpixel_fwd_kernel(const float* __restrict__ x, const float* __restrict__ w1, con
     }
     s += __shfl_xor(s, 1); s += __shfl_xor(s, 2); s += __shfl_xor(s, 4);
     if (part == 0 && row < mv) d[m0 + row] = 1.f / (1.f + expf(-s));
-    if (feat) {                   // context vector: mean of h2 over the pixels of each ROI (:70-74)
-        const float inv = 1.f / (float)pix_per_roi;
-        for (int e = threadIdx.x; e < DP_ROWS * 128; e += DP_THREADS) {
-            const int r = e >> 7, col = e & 127;
-            if (r < mv) atomicAdd(feat + (long long)((m0 + r) / pix_per_roi) * 128 + col, dp_img_load(img2, r, col) * inv);
-        }
-    }
+}
+
+// context vector: mean of h2 over the pixels of each ROI (:70-74).  One thread per (ROI, column) sums the ROI's rows of the
+// stored h2 in row order.  (Until round 13 the forward kernel added its 32 rows to feat with fp32 atomics: a 49-row ROI spans
+// two or three workgroups, so the sum's order -- and with it cls_prob, bbox_pred and every gradient of an ``ic`` net --
+// changed from run to run, under an ordered launch context too.)
+__global__ void dpixel_feat_kernel(const float* __restrict__ h2, float* __restrict__ feat, long long n_roi, int pix_per_roi) {
+    const long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x;
+    if (i >= n_roi * 128) return;
+    const float* p = h2 + (i >> 7) * pix_per_roi * 128 + (i & 127);
+    float s = 0.f;
+    for (int r = 0; r < pix_per_roi; ++r) s += p[(long long)r * 128];
+    feat[i] = s * (1.f / (float)pix_per_roi);
 }
 
 // backward chain.  w1t = W1^T (1024 x 512), w2t = W2^T (512 x 128): reduction-major copies made by the launcher.
@@ -400,10 +405,13 @@ extern "C" int32_t i2v_dpixel_fwd(const float* x, const float* w1, const float* 
         return true;
     }();
     (void)attr;
-    if (feat) hipMemsetAsync(feat, 0, sizeof(float) * (size_t)(M / pix_per_roi) * 128, st);
-    dpixel_fwd_kernel<<<i2v_cdiv(M, DP_ROWS), DP_THREADS, DP_LDS_FLOATS * 4, st>>>(x, w1, w2, w3, h1, h2, d, feat, M,
-                                                                                 pix_per_roi);
+    dpixel_fwd_kernel<<<i2v_cdiv(M, DP_ROWS), DP_THREADS, DP_LDS_FLOATS * 4, st>>>(x, w1, w2, w3, h1, h2, d, M);
     I2V_CHECK_LAUNCH("dpixel_fwd");
+    if (feat) {
+        const long long n_roi = M / pix_per_roi;
+        dpixel_feat_kernel<<<(unsigned)i2v_cdiv(n_roi * 128, 256), 256, 0, st>>>(h2, feat, n_roi, pix_per_roi);
+        I2V_CHECK_LAUNCH("dpixel_feat");
+    }
     return I2V_OK;
 }
 

@@ -670,7 +670,8 @@ int32_t i2v_signed_sqrt_bwd(const float* z, const float* g, float* gz, int64_t n
  * pixels) and its autograd backward incl. GradReverse (net_utils.py:52-61) with one kernel per direction: the 512-
  * and 128-wide activations of a 32-row tile stay in LDS between the layers.
  *   x (M,1024) rows = ROI pixels (NHWC order, M = R * pix_per_roi); w1 (512,1024), w2 (128,512), w3 (128); no biases.
- *   fwd writes h1 (M,512), h2 (M,128) (post-ReLU, kept for the backward), d (M) and, if feat != NULL, feat (R,128).
+ *   fwd writes h1 (M,512), h2 (M,128) (post-ReLU, kept for the backward), d (M) and, if feat != NULL, feat (R,128): the
+ *   mean of each ROI's h2 rows, summed in row order by a second small kernel (the same bits every run).
  *   bwd takes gd (M) (may be NULL) and gfeat (R,128) (may be NULL) and writes g3 (M) = grad at the conv3 output,
  *   gh2 (M,128), gh1 (M,512) -- the `gy` operands of the three filter gradients, which are plain
  *   i2v_conv_wgrad calls with KH = KW = 1 -- and gx (M,1024) = -lambda * d loss / d x. */

@@ -140,6 +140,19 @@ def _block(x, p, masks, mutate, last):
     return out, (p1.detach(), p2.detach(), p3.detach()), (m1, m2, mo)
 
 
+def chain_forward(h, params, masks=None, mutate=None):
+    """The blocks of ``chain`` as a differentiable function of ``h`` and of ``params`` (block dicts whose tensors already have
+    h's type; the caller decides which are leaves) -> (out, pre = [(p1, p2, p3)], masks = [(m1, m2, mo)] as booleans).  A larger
+    reference (tests/detector_head_ref.py: layer4 behind RoIAlign) composes this inside its own graph."""
+    pres, used = [], []
+    for i, p in enumerate(params):
+        m = None if masks is None else tuple(t.to(h.dtype) for t in masks[i])
+        h, pre, mk = _block(h, p, m, mutate, i == len(params) - 1)
+        pres.append(pre)
+        used.append(tuple(t > 0 for t in mk))
+    return h, pres, used
+
+
 def chain(x, blocks, gout, masks=None, in_mask=None, mutate=None, frozen=(), dtype=torch.float64):
     """x (B,C,H,W), ``blocks``: dicts of w1 w2 w3 wd (None: identity skip) s1 b1 .. sd bd stride, gout of the chain output's shape;
     ``masks``: per block (m1, m2, mo) boolean or None (``pre > 0``); ``in_mask``: the mask of the ReLU that produced x, applied to
@@ -149,18 +162,15 @@ def chain(x, blocks, gout, masks=None, in_mask=None, mutate=None, frozen=(), dty
         raise ValueError("unknown mutation %r" % (mutate,))
     leaf = x.detach().to(dtype).requires_grad_(True)
     h = leaf if in_mask is None else leaf * in_mask.to(dtype)
-    params, pres, used, wanted = [], [], [], []
+    params, wanted = [], []
     for i, blk in enumerate(blocks):
         p = {k: (v.detach().to(dtype) if torch.is_tensor(v) else v) for k, v in blk.items()}
         for name in NAMES:
             if p[name] is not None and (i, name) not in frozen:
                 p[name].requires_grad_(True)
                 wanted.append((i, name, p[name]))
-        m = None if masks is None else tuple(t.to(dtype) for t in masks[i])
-        h, pre, mk = _block(h, p, m, mutate, i == len(blocks) - 1)
         params.append(p)
-        pres.append(pre)
-        used.append(tuple(t > 0 for t in mk))
+    h, pres, used = chain_forward(h, params, masks, mutate)
     grads = torch.autograd.grad((h * gout.to(dtype)).sum(), [leaf] + [w for _, _, w in wanted])
     gw = [dict.fromkeys(NAMES) for _ in blocks]
     for (i, name, _), g in zip(wanted, grads[1:]):
