@@ -1238,6 +1238,67 @@ def recognition_align(rows, seg_off, seg_row, inst, n_classes, n_rel, device=Non
     return mean, count, top, hit, totals, per_class
 
 
+def _image_relation_device(device, what):
+    dev = torch.device(device if device is not None else "cuda")
+    if dev.type != "cuda":
+        raise _lib.I2VError("i2vsgg_amd ops run on the GPU only (got device %s); image_relations.%s is the host form" % (dev, what))
+    return dev
+
+
+def image_relation_match(pred_off, gt_off, pred_trip, pred_box, gt_trip, gt_box, iou_threshold=0.5, device=None):
+    """The greedy match of every image's ranked triplets against its annotated relations, one wave per (image, mode)
+    (include/i2vsgg_hip.h, i2v_image_relation_match; ``image_relations.pack`` builds the arrays).  Arrays or tensors: pred_off,
+    gt_off (I+1), pred_trip (n_pred,3), gt_trip (n_gt,3) int32; pred_box (n_pred,8), gt_box (n_gt,8) fp64.  Returns device
+    tensors, mode 0 relation and 1 phrase: (hit (2,n_pred) int32, hit_ov (2,n_pred) fp64, gt_rank (2,n_gt) int32)."""
+    dev = _image_relation_device(device, "match_host")
+    gc = np.diff(np.asarray(torch.as_tensor(gt_off).cpu()))
+    max_gt = max(int(gc.max()), 0) if len(gc) else 0
+    pred_off, gt_off, pred_trip, gt_trip = (_to_dev(x, torch.int32, dev) for x in (pred_off, gt_off, pred_trip, gt_trip))
+    pred_box, gt_box = _to_dev(pred_box, torch.float64, dev), _to_dev(gt_box, torch.float64, dev)
+    I, NP, NG = pred_off.numel() - 1, pred_trip.numel() // 3, gt_trip.numel() // 3
+    if (I < 0 or gt_off.numel() != I + 1 or pred_trip.numel() != 3 * NP or gt_trip.numel() != 3 * NG or pred_box.numel() != 8 * NP
+            or gt_box.numel() != 8 * NG):
+        raise ValueError("image_relation_match: array sizes do not agree")
+    hit = torch.full((2, NP), -1, device=dev, dtype=torch.int32)
+    hit_ov = torch.full((2, NP), -1.0, device=dev, dtype=torch.float64)
+    gt_rank = torch.full((2, NG), -1, device=dev, dtype=torch.int32)
+    with torch.cuda.device(dev):
+        ws = launch.workspace(lib.i2v_image_relation_match_workspace_bytes(I), dev, "image_relations")
+        check(lib.i2v_image_relation_match(ptr(pred_off), ptr(gt_off), ptr(pred_trip), ptr(pred_box), ptr(gt_trip), ptr(gt_box), I, NP,
+                                           NG, min(max_gt, 4096), float(iou_threshold), ptr(hit), ptr(hit_ov), ptr(gt_rank), ptr(ws),
+                                           ws.numel(), stream()), "image_relation_match")
+        if I > 0:
+            _video_status(ws, "image_relation_match", "image")
+    return hit, hit_ov, gt_rank
+
+
+def image_relation_count(gt_rank, gt_trip, gt_zs, nreturns, n_rel, device=None):
+    """The integer counters of recall@K from a match (include/i2vsgg_hip.h, i2v_image_relation_count).  gt_rank (2,n_gt),
+    gt_trip (n_gt,3), gt_zs (n_gt) int32; ``nreturns``: 1 to 8 values of K.  Returns device tensors (totals (2,K,2),
+    zs_totals (2,K,2), per_predicate (2,K,n_rel,2) int64): hits and ground truths per mode and K."""
+    dev = _image_relation_device(device, "count_host")
+    ks = np.ascontiguousarray(np.asarray(nreturns, np.int64).reshape(-1))
+    n_rel = int(n_rel)
+    if not 1 <= len(ks) <= 8 or (ks < 1).any() or (ks >= 2 ** 31).any():
+        raise ValueError("image_relation_count: nreturns holds 1 to 8 positive values of K (got %r)" % (list(nreturns),))
+    ks = ks.astype(np.int32)
+    gt_rank, gt_trip, gt_zs = (_to_dev(x, torch.int32, dev) for x in (gt_rank, gt_trip, gt_zs))
+    NG, K = gt_zs.numel(), len(ks)
+    if gt_rank.numel() != 2 * NG or gt_trip.numel() != 3 * NG or n_rel < 1:
+        raise ValueError("image_relation_count: array sizes do not agree")
+    totals = torch.zeros((2, K, 2), device=dev, dtype=torch.int64)
+    zs_totals = torch.zeros((2, K, 2), device=dev, dtype=torch.int64)
+    per_predicate = torch.zeros((2, K, n_rel, 2), device=dev, dtype=torch.int64)
+    with torch.cuda.device(dev):
+        ws = launch.workspace(lib.i2v_image_relation_match_workspace_bytes(0), dev, "image_relations")
+        check(lib.i2v_image_relation_count(ptr(gt_rank), ptr(gt_trip), ptr(gt_zs), ks.ctypes.data, NG, n_rel, K, ptr(totals),
+                                           ptr(zs_totals), ptr(per_predicate), ptr(ws), ws.numel(), stream()), "image_relation_count")
+        bad = int(ws[4:8].view(torch.int32).item())             # the caller reads the counters next anyway
+        if bad:
+            raise _lib.I2VError("image_relation_count: the predicate of ground truth %d lies outside [0, %d)" % (bad - 1, n_rel))
+    return totals, zs_totals, per_predicate
+
+
 def _det_eval_device(device, what):
     dev = torch.device(device if device is not None else "cuda")
     if dev.type != "cuda":

@@ -338,6 +338,44 @@ int32_t i2v_recognition_align(const double* rows, const int32_t* seg_off, const 
                               int32_t n_classes, int32_t n_rel, double* mean, int32_t* count, int32_t* top, int32_t* hit,
                               int64_t* totals, int64_t* per_class, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- Image relation recall@K: the greedy match per (image, mode) and the integer counters ------------------------
+ * Relation / phrase / predicate detection recall of image relation work (Lu et al., ECCV 2016) over what the relation test
+ * loop writes.  The reference has no image-level relation metric; the rules are this project's and are stated in full in
+ * i2vsgg_amd/image_relations.py, whose pack() builds the arrays.
+ *
+ * i2v_image_relation_match, one workgroup of one wave per (image, mode), mode 0 relation and 1 phrase: image i owns the
+ * predictions [pred_off[i], pred_off[i+1]), already in rank order, and the ground truths [gt_off[i], gt_off[i+1]) (at most
+ * max_gt <= I2V_IMAGE_RELATION_MAX_GT in one image).  pred_trip / gt_trip (n x 3 int32): subject class, predicate, object
+ * class; pred_box / gt_box (n x 8 fp64): subject box, object box (x1 y1 x2 y2 each).  The overlap is the +1-convention IoU
+ * in fp64 in the operation order of lib/model/nms/nms_cpu.py (a non-positive intersection side: 0); relation mode scores
+ * a candidate by min(overlap of the subjects, overlap of the objects), phrase mode by the overlap of the two union boxes
+ * (min of x1 / y1, max of x2 / y2).  The predictions are walked in order; each takes the not yet taken ground truth of
+ * its own triplet with the largest score >= iou_threshold, the lower index on equal scores.  Outputs, mode-major: hit
+ * (2 x n_pred int32: the ground truth within the image, or -1), hit_ov (2 x n_pred fp64: its score, or -1), gt_rank
+ * (2 x n_gt int32: the 0-based rank within the image of the prediction that took it, or -1).  The first int32 of the
+ * workspace is a status word: 0, or 1 + the largest index of an image whose offsets are not monotone, leave the arrays or
+ * hold more than max_gt ground truths; such an image comes out as -1 wherever its own range lies inside the arrays, and
+ * nothing is read through its entries.  Sized for the test loop's 100 predictions per image; any number is correct.
+ *
+ * i2v_image_relation_count, one thread per (mode, ground truth), after the match on the same stream: nreturns (n_k <=
+ * I2V_IMAGE_RELATION_MAX_K int32, HOST memory: read during the call) holds the values of K; ground truth g is hit at K when
+ * 0 <= gt_rank[mode][g] < K.  totals and zs_totals (2 x n_k x 2 int64): hits and ground truths per mode and K, over all
+ * ground truths and over those with gt_zs != 0; per_predicate (2 x n_k x n_rel x 2 int64): the same per predicate
+ * gt_trip[g][1].  The call clears the three tables itself.  The second int32 of the workspace (the match's workspace, or
+ * one of the same size) is a status word: 0, or 1 + the largest index of a ground truth whose predicate lies outside
+ * [0, n_rel); it is left out of every table. */
+#define I2V_IMAGE_RELATION_MAX_GT 4096
+#define I2V_IMAGE_RELATION_MAX_K 8
+size_t  i2v_image_relation_match_workspace_bytes(int32_t n_images);
+int32_t i2v_image_relation_match(const int32_t* pred_off, const int32_t* gt_off, const int32_t* pred_trip,
+                                 const double* pred_box, const int32_t* gt_trip, const double* gt_box, int32_t n_images,
+                                 int32_t n_pred, int32_t n_gt, int32_t max_gt, double iou_threshold, int32_t* hit,
+                                 double* hit_ov, int32_t* gt_rank, void* workspace, size_t workspace_bytes, void* stream);
+int32_t i2v_image_relation_count(const int32_t* gt_rank, const int32_t* gt_trip, const int32_t* gt_zs,
+                                 const int32_t* nreturns, int32_t n_gt, int32_t n_rel, int32_t n_k, int64_t* totals,
+                                 int64_t* zs_totals, int64_t* per_predicate, void* workspace, size_t workspace_bytes,
+                                 void* stream);
+
 /* ---- VOC detection evaluation that ends the detector test loop (lib/datasets/voc_eval.py:132-212) ----------------
  * Detections lie in results-file order (class, then image, then row; i2vsgg_amd/detection_eval.py pack()): det_key
  * (n_det int32) is the score as the results file would hold it ('%.3f'), in thousandths; det_box (n_det x 4 fp64) the
