@@ -103,6 +103,8 @@ SIGNATURES = {
     "i2v_image_relation_match_workspace_bytes": (_z, [_i]),
     "i2v_image_relation_match": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, C.c_double, _p, _p, _p, _p, _z, _p]),
     "i2v_image_relation_count": (_i, [_p, _p, _p, _p, _i, _i, _i, _p, _p, _p, _p, _z, _p]),
+    "i2v_relation_feature_pool_workspace_bytes": (_z, [_i]),
+    "i2v_relation_feature_pool": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p, _p, _p, _z, _p]),
     "i2v_det_eval_match_workspace_bytes": (_z, [_i]),
     "i2v_det_eval_match": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, C.c_double, _p, _p, _p, _p, _z, _p]),
     "i2v_det_eval_curve_workspace_bytes": (_z, [_i]),

@@ -12,7 +12,11 @@
 ``recognition_frame``  backbone forward + ``forward_predicate_eval`` + the device form of that tail for one frame.
 ``DetectStep``    ``detect_frame`` for several frames at a time as one replayable HIP graph (a branch per frame).
 ``RelationStep``  ``relation_frame`` + ``detection_output`` the same way.
+``keeping_relation_features``  a ``with`` block inside which ``relation_frame`` and every ``RelationStep`` built also hand the relation
+                  head's per-pair feature (``pre_feat``) to a sink (``relation_features.ArenaSink``), on the device.
 """
+import contextlib
+
 import numpy as np
 import torch
 
@@ -20,6 +24,23 @@ from . import launch, ops
 from .graphs import GraphRecorder, replay_graph
 from .model.utils.config import cfg
 from .staging import _Slot, _place_u8, parse_u8_meta, place_frames, step_uploader
+
+_FEATURE_SINK = [None]
+
+
+@contextlib.contextmanager
+def keeping_relation_features(sink):
+    """Inside the block the relation test loop keeps what it otherwise drops: ``relation_frame`` appends the frame's ``pre_feat`` and a
+    ``RelationStep`` built here has ``keep_features`` set and the sink's arena attached.  ``sink.attach(net)`` returns the store
+    (``append(key, rows)``), sized on first use from the network's annotations.  This is how a wrapper of a loop (``video_sgg_emb.py``
+    around ``test_sgg_emb.py``'s) asks for the features without the loop's code knowing; outside the block nothing changes."""
+    if _FEATURE_SINK[0] is not None:
+        raise RuntimeError("keeping_relation_features: a sink is active already")
+    _FEATURE_SINK[0] = sink
+    try:
+        yield sink
+    finally:
+        _FEATURE_SINK[0] = None
 
 
 class _FrameShape:
@@ -223,11 +244,25 @@ class RelationStep(_FrameGraphStep):
     are what ``relation_frame`` computes.  A frame with more boxes grows the capacity (graphs are captured again).
 
     ``step(im_data, im_info, im_paths)`` -> list over the frames of ``detection_output``'s five values (five Nones for a frame
-    with fewer than two boxes); ``step.run(batches)`` keeps one batch in flight while the host unpacks the previous one."""
+    with fewer than two boxes); ``step.run(batches)`` keeps one batch in flight while the host unpacks the previous one.
 
-    def __init__(self, net, frames=2, k=100, device="cuda:0", cap_boxes=9, use_graph=True, max_graphs=8):
+    ``keep_features=True`` also keeps the head's relation feature (``pre_feat``, ``emb_dim`` floats per ordered pair): the captured
+    body copies it into a static buffer ``feat (frames, cap_pairs, emb_dim)`` of its own (not part of ``out``: the pinned copy
+    of the triplets stays as small as it is), and ``launch()`` appends ``feat[f, :n_pairs_f]`` of every frame with at least two
+    boxes to ``self.arena`` (a ``relation_features.FeatureArena``, attached by the caller or by ``keeping_relation_features``, which
+    also sets the flag; keyed by the frame's entry of ``im_paths``) on the launching stream, right behind the replay.  The next replay cannot overwrite ``feat`` before the append has
+    read it: on a created stream the replay, the appends and the next replay are enqueued on that one stream in this order; on
+    the legacy default stream ``replay_graph`` runs the replay on its private stream between two event edges -- the appends are
+    enqueued on the caller's stream behind the edge that waits for the replay, and the next replay starts behind the edge that
+    waits for everything the caller's stream holds, the appends included.  With the default ``False`` no buffer, copy or graph
+    node is added."""
+
+    def __init__(self, net, frames=2, k=100, device="cuda:0", cap_boxes=9, use_graph=True, max_graphs=8, keep_features=False):
         super().__init__(net, frames, device, use_graph, max_graphs)
         self.k, self.n_rel = int(k), int(net.vrd.n_rel)
+        sink = _FEATURE_SINK[0]                      # keeping_relation_features: the block's sink asks for the features too
+        self.keep_features, self.feat = bool(keep_features) or sink is not None, None
+        self.arena = sink.attach(net) if sink is not None else None
         self._alloc(int(cap_boxes))
 
     def _alloc(self, cap_boxes):
@@ -241,6 +276,8 @@ class RelationStep(_FrameGraphStep):
         self.out = _Slot({"pair": ((F_, self.kk), torch.int32), "pred": ((F_, self.kk), torch.int32),
                           "conf": ((F_, self.kk), torch.float32)}, self.dev)
         self._host = [(torch.zeros(self.out.nbytes, dtype=torch.uint8).pin_memory(), torch.cuda.Event()) for _ in range(2)]
+        if self.keep_features:
+            self.feat = torch.zeros((F_, cp, int(self.net.vrd.emb_dim)), device=self.dev)
 
     def _frame(self, fs, f):
         from .model.faster_rcnn.faster_rcnn_SGG_emb import rasterize_masks
@@ -248,8 +285,10 @@ class RelationStep(_FrameGraphStep):
         with fs.ctx[f]:
             fmap = self.net.RCNN_base(fs.im[f:f + 1])
             rois, ix = v["rois"][f], v["ix"][f]
-            score, _ = self.net.vrd.forward_device(fmap, rois[:self.cap_boxes], None, rasterize_masks(v["bounds"][f], self.dev),
+            score, x = self.net.vrd.forward_device(fmap, rois[:self.cap_boxes], None, rasterize_masks(v["bounds"][f], self.dev),
                                                    ix[0], ix[1], rois=rois)
+            if self.keep_features:
+                self.feat[f].copy_(x)
             pair, pred, conf = ops.relation_topk(score, v["conf"][f], ix[0], ix[1], self.kk)
             o = self.out.views
             o["pair"][f].copy_(pair)
@@ -304,10 +343,14 @@ class RelationStep(_FrameGraphStep):
             conf[f, :nb] = np.asarray(a["scores"], np.float32).reshape(nb) if "scores" in a else 1
             meta.append((np.array(a["boxes"], np.float64).reshape(-1, 4), np.asarray(a["box_classes"]), ixs, ixo))
         self.inputs.write_host({"rois": rois, "bounds": bounds, "ix": ix, "conf": conf})
-        self._meta = meta
+        self._meta, self._keys = meta, list(im_paths)
 
     def launch(self):
         self._run_staged()
+        if self.keep_features and self.arena is not None:
+            for f, m in enumerate(self._meta):
+                if m is not None:
+                    self.arena.append(self._keys[f], self.feat[f, :len(m[2])])
         hb, ev = self._host[self._slot]
         hb.copy_(self.out.buf, non_blocking=True)
         ev.record(torch.cuda.current_stream(self.dev))
@@ -385,7 +428,11 @@ def relation_frame(net, im_data, im_info, im_path, k=100):
     """test_net_SGG_emb.py per-frame work: backbone, eval relation branch, top-k triplets."""
     fmap = net.RCNN_base(im_data)
     vrd_data = net.forward_relation_eval(fmap, im_info, im_path)
-    return vrd_data, detection_output(vrd_data, k)
+    out = detection_output(vrd_data, k)
+    sink = _FEATURE_SINK[0]
+    if sink is not None and out[1] is not None:          # keeping_relation_features: a frame with pairs has a slot
+        sink.attach(net).append(im_path, vrd_data["pre_feat"])
+    return vrd_data, out
 
 
 # lib/utils.py:579 ``np.log(0.5*(rel_so_prior+1.0/15))``: the reference's literal (VidVRD's 15 object classes), not derived from

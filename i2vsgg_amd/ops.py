@@ -1299,6 +1299,33 @@ def image_relation_count(gt_rank, gt_trip, gt_zs, nreturns, n_rel, device=None):
     return totals, zs_totals, per_predicate
 
 
+def relation_feature_pool(feat, slot_off, mem_off, mem_slot, mem_idx, device=None):
+    """The pooled feature of every video relation in one launch (include/i2vsgg_hip.h, i2v_relation_feature_pool;
+    ``relation_features.pack`` builds the tables, ``relation_features.pool_arrays_host`` is the numpy form).  feat (n_rows, dim)
+    fp32 (a device tensor is used where it lies), slot_off (S+1), mem_off (R+1), mem_slot (M), mem_idx (M) int32.  Returns
+    device tensors (pooled (R, dim) fp32, count (R) int32); a non-zero status word raises."""
+    dev = torch.device(device if device is not None else (feat.device if torch.is_tensor(feat) and feat.is_cuda else "cuda"))
+    if dev.type != "cuda":
+        raise _lib.I2VError("i2vsgg_amd ops run on the GPU only (got device %s); relation_features.pool_arrays_host is the host form" % dev)
+    feat = _to_dev(feat, torch.float32, dev)
+    if feat.dim() != 2 or feat.shape[1] < 1:
+        raise ValueError("relation_feature_pool: feat is a matrix (n_rows, dim) with dim >= 1")
+    slot_off, mem_off, mem_slot, mem_idx = (_to_dev(x, torch.int32, dev).reshape(-1) for x in (slot_off, mem_off, mem_slot, mem_idx))
+    N, D = feat.shape
+    S, R, M = slot_off.numel() - 1, mem_off.numel() - 1, mem_slot.numel()
+    if S < 0 or R < 0 or mem_idx.numel() != M:
+        raise ValueError("relation_feature_pool: array sizes do not agree")
+    pooled = torch.zeros((R, D), device=dev)
+    count = torch.zeros((R,), device=dev, dtype=torch.int32)
+    with torch.cuda.device(dev):
+        ws = launch.workspace(lib.i2v_relation_feature_pool_workspace_bytes(R), dev, "relation_features")
+        check(lib.i2v_relation_feature_pool(ptr(feat), ptr(slot_off), ptr(mem_off), ptr(mem_slot), ptr(mem_idx), N, S, R, M, D,
+                                            ptr(pooled), ptr(count), ptr(ws), ws.numel(), stream()), "relation_feature_pool")
+        if R > 0:
+            _video_status(ws, "relation_feature_pool", "relation")
+    return pooled, count
+
+
 def _det_eval_device(device, what):
     dev = torch.device(device if device is not None else "cuda")
     if dev.type != "cuda":

@@ -376,6 +376,30 @@ int32_t i2v_image_relation_count(const int32_t* gt_rank, const int32_t* gt_trip,
                                  int64_t* zs_totals, int64_t* per_predicate, void* workspace, size_t workspace_bytes,
                                  void* stream);
 
+/* ---- Video relation features: the per-frame pair features of a relation's members, pooled (lib/utils.py:100-132) ----
+ * generate_static_relation_feat of the reference: the feature of a video relation is the mean over its member frames of
+ * the row of pre_feat that the member's rel_idex names.  The rules are stated in full in i2vsgg_amd/relation_features.py,
+ * whose pack() builds the tables.
+ *
+ * i2v_relation_feature_pool, one wave per relation: feat (n_rows x dim fp32) holds the rows of every slot (a frame that had
+ * features of its own) one after another, slot s owning the rows [slot_off[s], slot_off[s+1]) (slot_off: n_slots+1 int32),
+ * row k of a slot being ordered pair k; relation r owns the members [mem_off[r], mem_off[r+1]) (mem_off: n_relations+1), in
+ * frame order; member i lies in slot mem_slot[i] (-1: the frame has no slot, the member is skipped) at pair mem_idx[i], i.e.
+ * at row slot_off[mem_slot[i]] + mem_idx[i].  pooled (n_relations x dim fp32) = per column the fp32 sum of the valid rows in
+ * member order -- the sum starts from the first valid row's value, not from +0.0, one add per row -- divided once, in fp32, by
+ * their number: np.array(rows).mean(axis=0) bit for bit; count (n_relations int32) = the number of valid rows.  A relation
+ * without a valid row has count 0 and a row of zeros (the reference writes NaN).  16-byte loads when dim % 4 == 0 and feat
+ * and pooled start on 16 bytes, 4-byte loads otherwise; any dim > 0.  The first int32 of the workspace is a status word: 0, or
+ * 1 + the largest index of a relation with an out-of-range table entry (mem_off not monotone or past n_members, a mem_slot
+ * below -1 or >= n_slots, a slot whose slot_off range is not monotone or leaves n_rows, a mem_idx outside its slot); such a
+ * relation comes out as count 0 and zeros, and nothing is read through its entries.  No floating-point atomics: two runs give
+ * the same bits. */
+size_t  i2v_relation_feature_pool_workspace_bytes(int32_t n_relations);
+int32_t i2v_relation_feature_pool(const float* feat, const int32_t* slot_off, const int32_t* mem_off,
+                                  const int32_t* mem_slot, const int32_t* mem_idx,
+                                  int32_t n_rows, int32_t n_slots, int32_t n_relations, int32_t n_members, int32_t dim,
+                                  float* pooled, int32_t* count, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- VOC detection evaluation that ends the detector test loop (lib/datasets/voc_eval.py:132-212) ----------------
  * Detections lie in results-file order (class, then image, then row; i2vsgg_amd/detection_eval.py pack()): det_key
  * (n_det int32) is the score as the results file would hold it ('%.3f'), in thousandths; det_box (n_det x 4 fp64) the

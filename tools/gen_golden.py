@@ -1194,13 +1194,59 @@ def gen_recognition():
          per_class=per_class, n_segments=np.array(len(pk.segments)), n_instances=np.array(len(pk.inst)))
 
 
+# ----------------------------------------------------------------------------- video relation features
+def gen_video_relation_feat():
+    """tests/golden/video_relation_feat.npz: the reference's generate_static_relation_feat (lib/utils.py:100-132) run in a temp
+    dir on the seeded inputs of tests/relation_feature_cases.golden_inputs().  The file holds data only, per case ``c<i>_``: the
+    frame features in loader order with their slot table (video index, frame number, row offsets), the relations (video index,
+    pno, duration, predicate name, rel_idex) and the contents of the .npy files the reference wrote."""
+    import tempfile
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import relation_feature_cases as cases
+    ns = _utils_functions(["generate_static_relation_feat"])
+    ns["os"] = os
+    out = {}
+    for c, case in enumerate(cases.golden_inputs()):
+        vids = list(case["relations"])
+        with tempfile.TemporaryDirectory() as tmp:
+            feat_dir, save_dir = os.path.join(tmp, "feat"), os.path.join(tmp, "video")
+            for vid, fno, rows in case["slots"]:
+                os.makedirs(os.path.join(feat_dir, vid), exist_ok=True)
+                np.savez(os.path.join(feat_dir, vid, str(fno)), pre_feat=rows)
+            ns["generate_static_relation_feat"](case["relations"], save_dir, feat_dir)
+            rel_vid, rel_pno, rel_dur, rel_pred, idex_off, idex, want = [], [], [], [], [0], [], []
+            for vid, rels in case["relations"].items():
+                for pno, rel in enumerate(rels):
+                    got = np.load(os.path.join(save_dir, rel["triplet"][1], "%s_%d.npy" % (vid, pno)))
+                    assert got.dtype == np.float32 and got.shape == (case["dim"],) and np.isfinite(got).all()
+                    rel_vid.append(vids.index(vid))
+                    rel_pno.append(pno)
+                    rel_dur.append(rel["duration"])
+                    rel_pred.append(rel["triplet"][1])
+                    idex.extend(rel["rel_idex"])
+                    idex_off.append(len(idex))
+                    want.append(got)
+        slot_off = np.zeros(len(case["slots"]) + 1, np.int32)
+        np.cumsum([len(s[2]) for s in case["slots"]], out=slot_off[1:])
+        p = "c%d_" % c
+        out.update({p + "vids": np.array(vids), p + "feat": np.concatenate([s[2] for s in case["slots"]]),
+                    p + "slot_vid": np.array([vids.index(s[0]) for s in case["slots"]], np.int32),
+                    p + "slot_fno": np.array([s[1] for s in case["slots"]], np.int32), p + "slot_off": slot_off,
+                    p + "rel_vid": np.array(rel_vid, np.int32), p + "rel_pno": np.array(rel_pno, np.int32),
+                    p + "rel_dur": np.array(rel_dur, np.int32).reshape(-1, 2), p + "rel_pred": np.array(rel_pred),
+                    p + "idex_off": np.array(idex_off, np.int32), p + "idex": np.array(idex, np.int32),
+                    p + "pooled": np.stack(want)})
+        print("  case %d: dim %d, %d frame files, %d relations" % (c, case["dim"], len(case["slots"]), len(want)))
+    save("video_relation_feat", "extracted", n_cases=np.array(len(cases.golden_inputs())), **out)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--only", default="")
     a = ap.parse_args()
     os.makedirs(GOLD, exist_ok=True)
     todo = a.only.split(",") if a.only else ["direct", "roialign", "roialign_fresh", "tails", "rpn", "nets", "full", "ctx", "step",
-                                             "vrd", "video", "det_eval", "recognition"]
+                                             "vrd", "video", "det_eval", "recognition", "video_relation_feat"]
     if "direct" in todo:
         print("[direct imports]")
         gen_direct()
@@ -1228,6 +1274,9 @@ def main():
     if "recognition" in todo:
         print("[predicate recognition: recognition_output / evaluate_recognition of lib/utils.py compiled from their own lines]")
         gen_recognition()
+    if "video_relation_feat" in todo:
+        print("[video relation features: generate_static_relation_feat of lib/utils.py compiled from its own lines]")
+        gen_video_relation_feat()
     if any(t in todo for t in ("rpn", "nets", "full", "vrd", "ctx", "step")):
         print("[imports with placeholders]")
         cfg = install_placeholders()
