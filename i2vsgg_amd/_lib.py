@@ -196,3 +196,9 @@ def ptr(t):
 def stream():
     import torch
     return torch.cuda.current_stream().cuda_stream
+
+
+def need_cuda(*ts):
+    for t in ts:
+        if t is not None and not t.is_cuda:
+            raise I2VError("i2vsgg_amd ops run on the GPU only (got a %s tensor); there is no CPU fallback" % t.device.type)

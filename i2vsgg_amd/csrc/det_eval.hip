@@ -7,7 +7,7 @@
 //
 // Layout (i2vsgg_amd/detection_eval.py pack()): detections lie in results-file order -- class, then image, then row --
 // so class c owns [cls_off[c], cls_off[c+1]) and a (class, image) pair with detections is one contiguous segment.
-#include "common.h"
+#include "table_common.h"
 
 #define DE_MAXG 4096         // ground truths of one (class, image): 64 lanes x 64 claimed bits in registers
 #define DE_TP 1
@@ -31,12 +31,12 @@ det_eval_match_kernel(const int* __restrict__ seg_det_off, const int* __restrict
     const int s = blockIdx.x, lane = threadIdx.x;
     const int d0 = seg_det_off[s], nd = seg_det_off[s + 1] - d0;
     const int slot = seg_gt[s];
-    bool bad = d0 < 0 || nd < 0 || (long long)d0 + nd > n_det || slot < 0 || slot >= n_slots;
+    bool bad = i2v_span_bad(d0, nd, n_det) || slot < 0 || slot >= n_slots;
     int g0 = 0, ng = 0;
     if (!bad) {
         g0 = gt_off[slot];
         ng = gt_off[slot + 1] - g0;
-        bad = g0 < 0 || ng < 0 || (long long)g0 + ng > n_gt || ng > max_gt || ng > DE_MAXG;
+        bad = i2v_span_bad(g0, ng, n_gt) || ng > max_gt || ng > DE_MAXG;
     }
     if (bad) {                                           // a malformed table: say so, touch nothing
         if (lane == 0) atomicMax(status, s + 1);
@@ -62,7 +62,7 @@ det_eval_match_kernel(const int* __restrict__ seg_det_off, const int* __restrict
         double best = -INFINITY;
         int bi = DE_NONE;
         for (int g = lane; g < ng; g += 64) {
-            const double* gb = gt_box + (size_t)(g0 + g) * 4;
+            const double* gb = gt_box + (size_t)(g0 + g) * 4;       // voc_eval's order, clamped: not i2v_overlap_plus1's arithmetic
             const double ixmin = gb[0] > b0 ? gb[0] : b0;
             const double iymin = gb[1] > b1 ? gb[1] : b1;
             const double ixmax = gb[2] < b2 ? gb[2] : b2;
@@ -99,8 +99,8 @@ det_eval_match_kernel(const int* __restrict__ seg_det_off, const int* __restrict
 }
 
 extern "C" size_t i2v_det_eval_match_workspace_bytes(int32_t n_det) {
-    if (n_det < 0) return 256;
-    return 256 + i2v_align((size_t)n_det * sizeof(int));                 // status word, per-segment order
+    if (n_det < 0) return I2V_STATUS_BYTES;
+    return I2V_STATUS_BYTES + i2v_align((size_t)n_det * sizeof(int));    // status word, per-segment order
 }
 
 extern "C" int32_t i2v_det_eval_match(const int32_t* seg_det_off, const int32_t* seg_gt, const int32_t* gt_off,
@@ -118,12 +118,10 @@ extern "C" int32_t i2v_det_eval_match(const int32_t* seg_det_off, const int32_t*
     I2V_CHECK_ARG(ws && ws_bytes >= i2v_det_eval_match_workspace_bytes(n_det), "det_eval_match: workspace too small");
     if (n_seg == 0 || n_det == 0) return I2V_OK;
     hipStream_t st = (hipStream_t)stream;
-    if (hipMemsetAsync(ws, 0, 4, st) != hipSuccess) {
-        i2v_set_error("det_eval_match: clearing the status word failed");
-        return I2V_ERR_LAUNCH;
-    }
+    I2V_CLEAR_STATUS(ws, 0, 4, st, "det_eval_match: clearing the status word failed");
     det_eval_match_kernel<<<n_seg, 64, 0, st>>>(seg_det_off, seg_gt, gt_off, det_key, det_box, gt_box, gt_hard, n_det, n_slots,
-                                                n_gt, max_gt, ovthresh, flag, ovmax, jmax, (int*)((char*)ws + 256), (int*)ws);
+                                                n_gt, max_gt, ovthresh, flag, ovmax, jmax, (int*)((char*)ws + I2V_STATUS_BYTES),
+                                                (int*)ws);
     I2V_CHECK_LAUNCH("det_eval_match");
     return I2V_OK;
 }
@@ -341,8 +339,9 @@ det_eval_curve_kernel(const unsigned long long* __restrict__ keys, const int* __
 }
 
 extern "C" size_t i2v_det_eval_curve_workspace_bytes(int32_t n_det) {
-    if (n_det <= 0) return 256;
-    return 256 + i2v_align((size_t)de_padded(n_det) * 8) + i2v_align((size_t)n_det * sizeof(double));   // status, keys, envelope
+    if (n_det <= 0) return I2V_STATUS_BYTES;
+    // status, keys, envelope
+    return I2V_STATUS_BYTES + i2v_align((size_t)de_padded(n_det) * 8) + i2v_align((size_t)n_det * sizeof(double));
 }
 
 extern "C" int32_t i2v_det_eval_curve(const int32_t* det_key, const int32_t* cls_off, const int32_t* flag, const int32_t* npos,
@@ -359,15 +358,12 @@ extern "C" int32_t i2v_det_eval_curve(const int32_t* det_key, const int32_t* cls
     if (n_cls == 0) return I2V_OK;
     hipStream_t st = (hipStream_t)stream;
     int* status = (int*)ws;
-    if (hipMemsetAsync(ws, 0, 4, st) != hipSuccess) {
-        i2v_set_error("det_eval_curve: clearing the status word failed");
-        return I2V_ERR_LAUNCH;
-    }
-    unsigned long long* keys = (unsigned long long*)((char*)ws + 256);
+    I2V_CLEAR_STATUS(ws, 0, 4, st, "det_eval_curve: clearing the status word failed");
+    unsigned long long* keys = (unsigned long long*)((char*)ws + I2V_STATUS_BYTES);
     double* env = nullptr;
     if (n_det > 0) {
         const int P = de_padded(n_det);
-        env = (double*)((char*)ws + 256 + i2v_align((size_t)P * 8));
+        env = (double*)((char*)ws + I2V_STATUS_BYTES + i2v_align((size_t)P * 8));
         det_eval_keys_kernel<<<i2v_cdiv(P, 256), 256, 0, st>>>(det_key, cls_off, n_cls, n_det, P, keys, status);
         const int tiles = P / DE_SORT_TILE;
         det_eval_sort_local<<<tiles, DE_SORT_THREADS, 0, st>>>(keys, 2, DE_SORT_TILE);

@@ -4,22 +4,11 @@
 // i2vsgg_amd/image_relations.py; the host form there evaluates the same float64 expressions in the same order (the library
 // is built with -ffp-contract=off -fno-fast-math), so device and host agree bit for bit.  No floating-point atomics; the
 // counters are integer atomics, whose result does not depend on the order.
-#include "common.h"
+#include "table_common.h"
 
 #define IR_MAXG I2V_IMAGE_RELATION_MAX_GT    // ground truths of one image: one taken-bit each in LDS
 #define IR_MAXK I2V_IMAGE_RELATION_MAX_K     // values of K in one count
 #define IR_NONE 0x7fffffff
-
-// lib/model/nms/nms_cpu.py:14,26-31 in its own operation order (+1 convention; an empty intersection: 0), as sq_overlap
-__device__ __forceinline__ double ir_overlap(const double* a, const double* b) {
-    const double iw = ((a[2] < b[2] ? a[2] : b[2]) - (a[0] > b[0] ? a[0] : b[0])) + 1.0;
-    const double ih = ((a[3] < b[3] ? a[3] : b[3]) - (a[1] > b[1] ? a[1] : b[1])) + 1.0;
-    if (iw <= 0.0 || ih <= 0.0) return 0.0;
-    const double inter = iw * ih;
-    const double aa = ((a[2] - a[0]) + 1.0) * ((a[3] - a[1]) + 1.0);
-    const double ab = ((b[2] - b[0]) + 1.0) * ((b[3] - b[1]) + 1.0);
-    return inter / ((aa + ab) - inter);
-}
 
 // the union of a row's subject and object box: min of x1 / y1, max of x2 / y2 (exact)
 __device__ __forceinline__ void ir_union(const double* r, double* u) {
@@ -40,8 +29,8 @@ image_relation_match_kernel(const int* __restrict__ pred_off, const int* __restr
     __shared__ unsigned int s_taken[IR_MAXG / 32];
     const int im = blockIdx.x, mode = blockIdx.y, lane = threadIdx.x;
     const int p0 = pred_off[im], p1 = pred_off[im + 1], g0 = gt_off[im], g1 = gt_off[im + 1];
-    const bool pred_ok = p0 >= 0 && p1 >= p0 && p1 <= n_pred;
-    const bool gt_ok = g0 >= 0 && g1 >= g0 && g1 <= n_gt;
+    const bool pred_ok = !i2v_range_bad(p0, p1, n_pred);
+    const bool gt_ok = !i2v_range_bad(g0, g1, n_gt);
     int* hit_m = hit + (size_t)mode * n_pred;
     double* hov_m = hit_ov + (size_t)mode * n_pred;
     int* rank_m = gt_rank + (size_t)mode * n_gt;
@@ -71,12 +60,12 @@ image_relation_match_kernel(const int* __restrict__ pred_off, const int* __restr
             const double* gb = gt_box + (size_t)(g0 + g) * 8;
             double ov;
             if (mode == 0) {
-                const double a = ir_overlap(pb, gb), b = ir_overlap(pb + 4, gb + 4);
+                const double a = i2v_overlap_plus1(pb, gb), b = i2v_overlap_plus1(pb + 4, gb + 4);
                 ov = a < b ? a : b;
             } else {
                 double gu[4];
                 ir_union(gb, gu);
-                ov = ir_overlap(pu, gu);
+                ov = i2v_overlap_plus1(pu, gu);
             }
             if (ov >= thr && (bi == IR_NONE || ov > best)) best = ov, bi = g;   // ascending g: the lower index stays on equal ov
         }
@@ -151,7 +140,7 @@ image_relation_count_kernel(const int* __restrict__ gt_rank, const int* __restri
 
 extern "C" size_t i2v_image_relation_match_workspace_bytes(int32_t n_images) {
     (void)n_images;
-    return 256;                                                  // two status words: match, count
+    return I2V_STATUS_BYTES;                                     // two status words: match, count
 }
 
 extern "C" int32_t i2v_image_relation_match(const int32_t* pred_off, const int32_t* gt_off, const int32_t* pred_trip,
@@ -167,10 +156,7 @@ extern "C" int32_t i2v_image_relation_match(const int32_t* pred_off, const int32
     I2V_CHECK_ARG(n_gt == 0 || (gt_trip && gt_box && gt_rank), "image_relation_match: null pointer");
     I2V_CHECK_ARG(ws && ws_bytes >= i2v_image_relation_match_workspace_bytes(n_images), "image_relation_match: workspace too small");
     hipStream_t st = (hipStream_t)stream;
-    if (hipMemsetAsync(ws, 0, 8, st) != hipSuccess) {
-        i2v_set_error("image_relation_match: clearing the status words failed");
-        return I2V_ERR_LAUNCH;
-    }
+    I2V_CLEAR_STATUS(ws, 0, 8, st, "image_relation_match: clearing the status words failed");
     if (n_images == 0) return I2V_OK;
     image_relation_match_kernel<<<dim3(n_images, 2), I2V_WAVE, 0, st>>>(pred_off, gt_off, pred_trip, pred_box, gt_trip, gt_box, n_pred,
                                                                        n_gt, max_gt, iou_threshold, hit, hit_ov, gt_rank, (int*)ws);
@@ -191,8 +177,9 @@ extern "C" int32_t i2v_image_relation_count(const int32_t* gt_rank, const int32_
     for (int k = 0; k < IR_MAXK; ++k) ks.k[k] = k < n_k ? nreturns[k] : 0;
     hipStream_t st = (hipStream_t)stream;
     const size_t cells = (size_t)2 * n_k * 2 * sizeof(int64_t);
-    if (hipMemsetAsync((char*)ws + 4, 0, 4, st) != hipSuccess || hipMemsetAsync(totals, 0, cells, st) != hipSuccess ||
-        hipMemsetAsync(zs_totals, 0, cells, st) != hipSuccess || hipMemsetAsync(per_predicate, 0, cells * n_rel, st) != hipSuccess) {
+    I2V_CLEAR_STATUS(ws, 4, 4, st, "image_relation_count: clearing the counters failed");
+    if (hipMemsetAsync(totals, 0, cells, st) != hipSuccess || hipMemsetAsync(zs_totals, 0, cells, st) != hipSuccess ||
+        hipMemsetAsync(per_predicate, 0, cells * n_rel, st) != hipSuccess) {
         i2v_set_error("image_relation_count: clearing the counters failed");
         return I2V_ERR_LAUNCH;
     }

@@ -4,7 +4,7 @@
 // in i2vsgg_amd/eval.py evaluate the same expressions in the same order (the library is built with -ffp-contract=off
 // -fno-fast-math), so device and host agree bit for bit.  No floating-point atomics: every sum has a fixed order; the counters
 // are integer atomics, whose result does not depend on the order.
-#include "common.h"
+#include "table_common.h"
 
 #define REC_TOP 10           // slots of a ranking (np.argsort(-x)[:10])
 #define REC_MAX_W I2V_RECOGNITION_MAX_WIDTH
@@ -69,7 +69,7 @@ recognition_segments_kernel(const double* __restrict__ rows, const int* __restri
     const int s = blockIdx.x, lane = threadIdx.x;
     const int W = 2 * C + R;
     const int o0 = seg_off[s], o1 = seg_off[s + 1];
-    int bad = (o0 < 0 || o1 < o0 || o1 > M) ? 1 : 0;
+    int bad = i2v_range_bad(o0, o1, M) ? 1 : 0;
     if (!bad) {
         for (int i = o0 + lane; i < o1; i += I2V_WAVE) {
             const int r = seg_row[i];
@@ -158,7 +158,7 @@ recognition_hits_kernel(const int* __restrict__ inst, const int* __restrict__ co
 
 extern "C" size_t i2v_recognition_rows_workspace_bytes(int32_t n_pairs) {
     (void)n_pairs;
-    return 256;                                                  // the status word
+    return I2V_STATUS_BYTES;                                     // the status word
 }
 
 extern "C" int32_t i2v_recognition_rows(const float* cls_prob, const float* rel_prob, const int64_t* ixs, const int64_t* ixo,
@@ -172,10 +172,7 @@ extern "C" int32_t i2v_recognition_rows(const float* cls_prob, const float* rel_
     I2V_CHECK_ARG(n_pairs == 0 || (cls_prob && rel_prob && ixs && ixo && L && sub && obj && pre), "recognition_rows: null pointer");
     I2V_CHECK_ARG(ws && ws_bytes >= i2v_recognition_rows_workspace_bytes(n_pairs), "recognition_rows: workspace too small");
     hipStream_t st = (hipStream_t)stream;
-    if (hipMemsetAsync(ws, 0, 8, st) != hipSuccess) {
-        i2v_set_error("recognition_rows: clearing the status word failed");
-        return I2V_ERR_LAUNCH;
-    }
+    I2V_CLEAR_STATUS(ws, 0, 8, st, "recognition_rows: clearing the status word failed");
     if (n_pairs + n_boxes == 0) return I2V_OK;
     recognition_rows_kernel<<<n_pairs + n_boxes, I2V_WAVE, 0, st>>>(cls_prob, rel_prob, (const long long*)ixs, (const long long*)ixo,
                                                                    L, n_boxes, n_pairs, n_classes, n_rel, sub, obj, pre, cls,
@@ -187,7 +184,7 @@ extern "C" int32_t i2v_recognition_rows(const float* cls_prob, const float* rel_
 extern "C" size_t i2v_recognition_align_workspace_bytes(int32_t n_segments, int32_t n_instances) {
     (void)n_segments;
     (void)n_instances;
-    return 256;                                                  // two status words: segments, instances
+    return I2V_STATUS_BYTES;                                     // two status words: segments, instances
 }
 
 extern "C" int32_t i2v_recognition_align(const double* rows, const int32_t* seg_off, const int32_t* seg_row, const int32_t* inst,
@@ -208,7 +205,8 @@ extern "C" int32_t i2v_recognition_align(const double* rows, const int32_t* seg_
     I2V_CHECK_ARG(ws && ws_bytes >= i2v_recognition_align_workspace_bytes(n_segments, n_instances),
                   "recognition_align: workspace too small");
     hipStream_t st = (hipStream_t)stream;
-    if (hipMemsetAsync(ws, 0, 8, st) != hipSuccess || hipMemsetAsync(totals, 0, 8 * sizeof(int64_t), st) != hipSuccess ||
+    I2V_CLEAR_STATUS(ws, 0, 8, st, "recognition_align: clearing the counters failed");
+    if (hipMemsetAsync(totals, 0, 8 * sizeof(int64_t), st) != hipSuccess ||
         hipMemsetAsync(per_class, 0, (size_t)n_classes * 4 * sizeof(int64_t), st) != hipSuccess) {
         i2v_set_error("recognition_align: clearing the counters failed");
         return I2V_ERR_LAUNCH;

@@ -3,7 +3,7 @@
 // i2vsgg_amd/relation_features.py; the host form there (pool_arrays_host) adds the same float32 values in the same order, so
 // device and host agree bit for bit (the library is built with -ffp-contract=off -fno-fast-math).  No floating-point atomics,
 // no LDS, no barrier: a relation belongs to one wave, its rows are added in member order, two runs give the same bits.
-#include "common.h"
+#include "table_common.h"
 
 #define RF_WAVES 4           // relations of one workgroup, one per wave; the waves never meet
 #define RF_BATCH 4           // rows whose loads are in flight together (the adds stay in member order)
@@ -46,7 +46,7 @@ __device__ __forceinline__ int rf_validate(const int* __restrict__ slot_off, con
             continue;
         }
         const int b = slot_off[s], e = slot_off[s + 1];
-        if (b < 0 || e < b || e > n_rows) {
+        if (i2v_range_bad(b, e, n_rows)) {
             bad = 1;
             continue;
         }
@@ -75,7 +75,7 @@ relation_feature_pool_kernel(const float* __restrict__ feat, const int* __restri
     if (r >= n_relations) return;                                            // a whole wave leaves: no barrier follows
     const int m0 = mem_off[r], m1 = mem_off[r + 1];
     int n = -1;
-    if (m0 >= 0 && m1 >= m0 && m1 <= n_members) n = rf_validate(slot_off, mem_slot, mem_idx, m0, m1, n_rows, n_slots, lane);
+    if (!i2v_range_bad(m0, m1, n_members)) n = rf_validate(slot_off, mem_slot, mem_idx, m0, m1, n_rows, n_slots, lane);
     if (n < 0) {                                                             // a malformed relation: say so, read nothing more
         if (lane == 0) atomicMax(status, r + 1);
         n = 0;
@@ -138,7 +138,7 @@ relation_feature_pool_kernel(const float* __restrict__ feat, const int* __restri
 
 extern "C" size_t i2v_relation_feature_pool_workspace_bytes(int32_t n_relations) {
     (void)n_relations;
-    return 256;                                                              // the status word
+    return I2V_STATUS_BYTES;                                                 // the status word
 }
 
 extern "C" int32_t i2v_relation_feature_pool(const float* feat, const int32_t* slot_off, const int32_t* mem_off,
@@ -154,10 +154,7 @@ extern "C" int32_t i2v_relation_feature_pool(const float* feat, const int32_t* s
     I2V_CHECK_ARG(ws && ws_bytes >= i2v_relation_feature_pool_workspace_bytes(n_relations),
                   "relation_feature_pool: workspace too small");
     hipStream_t st = (hipStream_t)stream;
-    if (hipMemsetAsync(ws, 0, 4, st) != hipSuccess) {
-        i2v_set_error("relation_feature_pool: clearing the status word failed");
-        return I2V_ERR_LAUNCH;
-    }
+    I2V_CLEAR_STATUS(ws, 0, 4, st, "relation_feature_pool: clearing the status word failed");
     if (n_relations == 0) return I2V_OK;
     const int blocks = i2v_cdiv(n_relations, RF_WAVES);
     // 16-byte loads need rows that start on 16 bytes: dim a multiple of 4 and both bases aligned

@@ -3,7 +3,7 @@
 // shape.  The rules are stated once, in i2vsgg_amd/relation_targets.py; the host form there and these kernels evaluate the same
 // float64 expressions in the same order (the library is built with -ffp-contract=off -fno-fast-math) and every decision of a
 // draw is integer arithmetic, so they agree bit for bit.  No floating-point atomics; two runs give the same bits.
-#include "common.h"
+#include "table_common.h"
 
 #define RT_CAP 64            // detections of one frame: lane a is detection a (relation_targets.CAP)
 #define RT_DRAWS 10          // draws per annotated relation
@@ -11,17 +11,6 @@
 #define RT_B 64              // rows of a frame in the padded box table
 #define RT_EMIT_THREADS 256
 #define RT_MARGIN 10.0       // of the union box (build_pair_tables)
-
-// lib/model/nms/nms_cpu.py:14,26-31 in its own operation order (+1 convention; an empty intersection: 0)
-__device__ __forceinline__ double rt_overlap(const double* a, const double* b) {
-    const double iw = ((a[2] < b[2] ? a[2] : b[2]) - (a[0] > b[0] ? a[0] : b[0])) + 1.0;
-    const double ih = ((a[3] < b[3] ? a[3] : b[3]) - (a[1] > b[1] ? a[1] : b[1])) + 1.0;
-    if (iw <= 0.0 || ih <= 0.0) return 0.0;
-    const double inter = iw * ih;
-    const double aa = ((a[2] - a[0]) + 1.0) * ((a[3] - a[1]) + 1.0);
-    const double ab = ((b[2] - b[0]) + 1.0) * ((b[3] - b[1]) + 1.0);
-    return inter / ((aa + ab) - inter);
-}
 
 // the integer weight of a candidate: both overlaps are in [0.5, 1], so it lies in [16384, 65536]
 __device__ __forceinline__ unsigned long long rt_weight(double ia, double ib) {
@@ -54,9 +43,9 @@ __device__ int rt_frame_bad(const RtTables& T, int f) {
     const int d0 = T.det_off[f], d1 = T.det_off[f + 1], g0 = T.gt_off[f], g1 = T.gt_off[f + 1];
     const int r0 = T.rel_off[f], r1 = T.rel_off[f + 1];
     int bad = 0;
-    if (d0 < 0 || d1 < d0 || d1 > T.n_det || d1 - d0 > RT_CAP) bad = 1;
-    if (g0 < 0 || g1 < g0 || g1 > T.n_gt) bad = 1;
-    if (r0 < 0 || r1 < r0 || r1 > T.n_relations) bad = 1;
+    if (i2v_range_bad(d0, d1, T.n_det) || d1 - d0 > RT_CAP) bad = 1;
+    if (i2v_range_bad(g0, g1, T.n_gt)) bad = 1;
+    if (i2v_range_bad(r0, r1, T.n_relations)) bad = 1;
     const double h = T.ih[f], w = T.iw[f];
     if (!(h > 0.0) || !(w > 0.0) || !(h <= 1.0e9) || !(w <= 1.0e9)) bad = 1;
     for (int j = tid; j < f; j += nt)
@@ -88,8 +77,8 @@ relation_sample_kernel(RtTables T, int* __restrict__ samp) {
         const int gs = g0 + T.rel[(long long)r * 3], go = g0 + T.rel[(long long)r * 3 + 1];
         double bs[4], bo[4];
         for (int k = 0; k < 4; ++k) bs[k] = T.gt_box[(long long)gs * 4 + k], bo[k] = T.gt_box[(long long)go * 4 + k];
-        const double is = lane < nd ? rt_overlap(box, bs) : 0.0;
-        const double io = lane < nd ? rt_overlap(box, bo) : 0.0;
+        const double is = lane < nd ? i2v_overlap_plus1(box, bs) : 0.0;
+        const double io = lane < nd ? i2v_overlap_plus1(box, bo) : 0.0;
         const bool ms = lane < nd && cls == T.gt_cls[gs] && is >= 0.5;
         const bool mo = lane < nd && cls == T.gt_cls[go] && io >= 0.5;
         const unsigned long long word_o = __ballot(mo);  // the subject side needs no word: lane a holds its own bit, ms
@@ -231,7 +220,7 @@ relation_emit_kernel(RtTables T, const int* __restrict__ samp, float* __restrict
 
 extern "C" size_t i2v_relation_targets_workspace_bytes(int32_t n_frames) {
     (void)n_frames;
-    return 256;                                          // the status word
+    return I2V_STATUS_BYTES;                             // the status word
 }
 
 extern "C" int32_t i2v_relation_targets(const int32_t* det_off, const double* det_box, const int32_t* det_cls,
@@ -252,8 +241,8 @@ extern "C" int32_t i2v_relation_targets(const int32_t* det_off, const double* de
     I2V_CHECK_ARG(n_gt == 0 || (gt_box && gt_cls), "relation_targets: null pointer");
     I2V_CHECK_ARG(rel5 && bounds && ixs && ixo && w && n_pairs && n_dropped && (n_pred == 0 || labels), "relation_targets: null pointer");
     hipStream_t st = (hipStream_t)stream;
-    if (hipMemsetAsync(ws, 0, 4, st) != hipSuccess ||
-        (n_relations > 0 && hipMemsetAsync(samp, 0xff, (size_t)n_relations * RT_DRAWS * 2 * sizeof(int32_t), st) != hipSuccess)) {
+    I2V_CLEAR_STATUS(ws, 0, 4, st, "relation_targets: clearing the status word / the draws failed");
+    if (n_relations > 0 && hipMemsetAsync(samp, 0xff, (size_t)n_relations * RT_DRAWS * 2 * sizeof(int32_t), st) != hipSuccess) {
         i2v_set_error("relation_targets: clearing the status word / the draws failed");
         return I2V_ERR_LAUNCH;
     }

@@ -3,7 +3,7 @@
 // All arithmetic that decides something is float64 in the reference's operation order (the library is built with
 // -ffp-contract=off -fno-fast-math, so every + - * / rounds once, like the CPU's).  No floating-point atomics; every
 // reduction has a fixed order, so two runs give the same bits.
-#include "common.h"
+#include "table_common.h"
 
 #define VA_MAXP 100          // predictions of one frame that take part (max_traj_num_in_clip)
 #define VA_THREADS 256       // thread (p, h) = (t & 127, t >> 7): prediction p against the ranked candidates 64h .. 64h+63
@@ -26,7 +26,7 @@ __device__ __forceinline__ int va_rank_desc(const double* key, int n, int i) {
     return r;
 }
 
-// lib/utils.py:20-32 in its own operation order (no +1; empty or touching intersection: 0)
+// lib/utils.py:20-32 in its own operation order (no +1; empty or touching intersection: 0): not i2v_overlap_plus1's arithmetic
 __device__ __forceinline__ double va_iou(const double* a, const double* b) {
     const double left = a[0] > b[0] ? a[0] : b[0];
     const double right = a[2] < b[2] ? a[2] : b[2];
@@ -65,7 +65,7 @@ video_associate_kernel(const int* __restrict__ frame_off, const int* __restrict_
     __shared__ int s_next;
     const int v = blockIdx.x, t = threadIdx.x;
     int f0 = frame_off[v], f1 = frame_off[v + 1];
-    if (f0 < 0 || f1 < f0 || f1 > n_frames) {            // a malformed table: say so, touch nothing
+    if (i2v_range_bad(f0, f1, n_frames)) {               // a malformed table: say so, touch nothing
         if (t == 0) {
             atomicMax(status, n_frames + 1);
             n_rel[v] = 0;
@@ -77,7 +77,7 @@ video_associate_kernel(const int* __restrict__ frame_off, const int* __restrict_
     for (int f = f0; f < f1; ++f) {
         int p0 = pred_off[f];
         int n = pred_off[f + 1] - p0;
-        if (p0 < 0 || n < 0 || n > max_per_frame || n > VA_MAXP || (long long)p0 + n > n_preds) {
+        if (n > max_per_frame || n > VA_MAXP || i2v_span_bad(p0, n, n_preds)) {
             if (t == 0) atomicMax(status, f + 1);        // the frame is skipped as if empty; the caller reads the status
             n = 0;
             p0 = 0;
@@ -177,7 +177,7 @@ video_associate_kernel(const int* __restrict__ frame_off, const int* __restrict_
 
 extern "C" size_t i2v_video_associate_workspace_bytes(int32_t n_videos, int32_t n_frames, int32_t n_preds) {
     (void)n_videos; (void)n_frames; (void)n_preds;
-    return 256;                                          // the status word
+    return I2V_STATUS_BYTES;                             // the status word
 }
 
 extern "C" int32_t i2v_video_associate(const int32_t* frame_off, const int32_t* frame_no, const int32_t* pred_off,
@@ -189,17 +189,14 @@ extern "C" int32_t i2v_video_associate(const int32_t* frame_off, const int32_t* 
     I2V_CHECK_ARG(max_per_frame >= 0 && max_per_frame <= VA_MAXP,
                   "video_associate: at most %d predictions of a frame take part (got %d): cut each frame's list first", VA_MAXP,
                   max_per_frame);
-    I2V_CHECK_ARG(frame_off && frame_no && pred_off && n_rel, "video_associate: null pointer");
+    I2V_CHECK_ARG(frame_off && pred_off && (n_frames == 0 || frame_no) && (n_videos == 0 || n_rel), "video_associate: null pointer");
     I2V_CHECK_ARG(n_preds == 0 || (score && triplet && boxes && rel_id && rel_start && rel_len && rel_score),
                   "video_associate: null pointer");
     I2V_CHECK_ARG(ws && ws_bytes >= i2v_video_associate_workspace_bytes(n_videos, n_frames, n_preds),
                   "video_associate: workspace too small");
     if (n_videos == 0) return I2V_OK;
     hipStream_t st = (hipStream_t)stream;
-    if (hipMemsetAsync(ws, 0, 4, st) != hipSuccess) {
-        i2v_set_error("video_associate: clearing the status word failed");
-        return I2V_ERR_LAUNCH;
-    }
+    I2V_CLEAR_STATUS(ws, 0, 4, st, "video_associate: clearing the status word failed");
     video_associate_kernel<<<n_videos, VA_THREADS, 0, st>>>(frame_off, frame_no, pred_off, score, triplet, boxes, n_frames,
                                                             n_preds, max_per_frame, rel_id, rel_start, rel_len, rel_score,
                                                             n_rel, (int*)ws);
@@ -314,8 +311,7 @@ video_match_kernel(const int* __restrict__ pred_off, const double* __restrict__ 
     const int p0 = pred_off[v], np = pred_off[v + 1] - p0;
     const int g0 = gt_off[v];
     int ng = gt_off[v + 1] - g0;
-    if (p0 < 0 || np < 0 || np > max_pred || np > VM_MAXP || (long long)p0 + np > n_pred || g0 < 0 || ng < 0 || ng > max_gt ||
-        ng > VM_MAXG || (long long)g0 + ng > n_gt) {
+    if (np > max_pred || np > VM_MAXP || i2v_span_bad(p0, np, n_pred) || ng > max_gt || ng > VM_MAXG || i2v_span_bad(g0, ng, n_gt)) {
         if (lane == 0) atomicMax(status, v + 1);
         return;
     }
@@ -352,8 +348,8 @@ video_match_kernel(const int* __restrict__ pred_off, const double* __restrict__ 
 }
 
 extern "C" size_t i2v_video_viou_match_workspace_bytes(int32_t n_pred, int32_t n_gt) {
-    if (n_pred < 0 || n_gt < 0) return 256;
-    return 256 + i2v_align(2 * ((size_t)n_pred + n_gt) * sizeof(double));     // status word, trajectory volumes
+    if (n_pred < 0 || n_gt < 0) return I2V_STATUS_BYTES;
+    return I2V_STATUS_BYTES + i2v_align(2 * ((size_t)n_pred + n_gt) * sizeof(double));     // status word, trajectory volumes
 }
 
 extern "C" int32_t i2v_video_viou_match(const int32_t* pred_off, const int32_t* pred_rel, const double* pred_score,
@@ -375,11 +371,8 @@ extern "C" int32_t i2v_video_viou_match(const int32_t* pred_off, const int32_t* 
     if (n_videos == 0 || n_pred == 0) return I2V_OK;
     hipStream_t st = (hipStream_t)stream;
     int* status = (int*)ws;
-    double* vol = (double*)((char*)ws + 256);
-    if (hipMemsetAsync(ws, 0, 4, st) != hipSuccess) {
-        i2v_set_error("video_viou_match: clearing the status word failed");
-        return I2V_ERR_LAUNCH;
-    }
+    double* vol = (double*)((char*)ws + I2V_STATUS_BYTES);
+    I2V_CLEAR_STATUS(ws, 0, 4, st, "video_viou_match: clearing the status word failed");
     video_volume_kernel<<<i2v_cdiv(2ll * ((long long)n_pred + n_gt), 4), 256, 0, st>>>(pred_rel, gt_rel, boxes, n_pred, n_gt,
                                                                                        n_boxes, vol);
     if (max_gt > 0)

@@ -29,6 +29,8 @@ from the same packed arrays and agree bit for bit.
 """
 import numpy as np
 
+from .packing import cat, offsets
+
 MAX_GT = 4096                # ground truths of one class in one image (csrc/det_eval.hip DE_MAXG)
 MAX_CLASSES = 255            # foreground classes
 MAX_PER_CLASS = 1 << 24      # detections of one class
@@ -112,13 +114,11 @@ def pack(all_boxes, roidb, num_classes):
     seg_cls, seg_img, seg_n = np.asarray(seg_cls, np.int32), np.asarray(seg_img, np.int32), np.asarray(seg_n, np.int64)
     if seg_n.sum() >= 2 ** 30:
         raise ValueError("detection_eval: too many detections")
-    seg_det_off = np.zeros(len(seg_n) + 1, np.int32)
-    np.cumsum(seg_n, out=seg_det_off[1:])
+    seg_det_off = offsets(seg_n, "detection_eval: too many detections")
     per_class = np.bincount(seg_cls, weights=seg_n, minlength=C).astype(np.int64) if C else np.zeros(0, np.int64)
     if len(per_class) and per_class.max() >= MAX_PER_CLASS:
         raise ValueError("detection_eval: at most %d detections of one class" % (MAX_PER_CLASS - 1))
-    cls_off = np.zeros(C + 1, np.int32)
-    np.cumsum(per_class, out=cls_off[1:])
+    cls_off = offsets(per_class, "detection_eval: too many detections")
     det_img = np.repeat(seg_img, seg_n).astype(np.int32)
 
     g_box, g_cls, g_img, g_hard, g_row = [], [], [], [], []
@@ -133,9 +133,8 @@ def pack(all_boxes, roidb, num_classes):
         g_img.append(np.full(len(cl), i, np.int64))
         g_hard.append((hard != 0).astype(np.int32))
         g_row.append(np.arange(len(cl), dtype=np.int32))
-    cat = lambda xs, shape, dt: np.concatenate(xs).astype(dt) if xs else np.zeros(shape, dt)
-    g_box, g_cls, g_img = cat(g_box, (0, 4), np.float64), cat(g_cls, (0,), np.int64), cat(g_img, (0,), np.int64)
-    g_hard, g_row = cat(g_hard, (0,), np.int32), cat(g_row, (0,), np.int32)
+    g_box, g_cls, g_img = cat(g_box, (4,), np.float64), cat(g_cls, (), np.int64), cat(g_img, (), np.int64)
+    g_hard, g_row = cat(g_hard, (), np.int32), cat(g_row, (), np.int32)
     fg = (g_cls >= 1) & (g_cls < num_classes)
     g_box, g_cls, g_img, g_hard, g_row = g_box[fg], g_cls[fg], g_img[fg], g_hard[fg], g_row[fg]
     slot = (g_cls - 1) * I + g_img
@@ -143,8 +142,7 @@ def pack(all_boxes, roidb, num_classes):
     counts = np.bincount(slot, minlength=C * I) if C * I else np.zeros(0, np.int64)
     if len(counts) and counts.max() > MAX_GT:
         raise ValueError("detection_eval: at most %d ground truths of one class in one image (got %d)" % (MAX_GT, counts.max()))
-    gt_off = np.zeros(C * I + 1, np.int32)
-    np.cumsum(counts, out=gt_off[1:])
+    gt_off = offsets(counts, "detection_eval: too many ground truths")
     npos = np.bincount(g_cls[g_hard == 0] - 1, minlength=C).astype(np.int32) if C else np.zeros(0, np.int32)
     return Packed(n_classes=C, n_images=I, det_key=det_key, det_box=det_box, det_img=det_img, cls_off=cls_off,
                   seg_det_off=seg_det_off, seg_cls=seg_cls, seg_img=seg_img, seg_gt=(seg_cls.astype(np.int64) * I + seg_img).astype(np.int32),

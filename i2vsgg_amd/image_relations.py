@@ -33,7 +33,7 @@ Predictions.
   or coordinate is a ``ValueError``.
 
 Overlap.
-  Float64, +1 pixel convention, in the operation order of ``seqnms._overlap`` (lib/model/nms/nms_cpu.py:14,26-31):
+  Float64, +1 pixel convention, in the operation order of ``packing.overlap_plus1`` (lib/model/nms/nms_cpu.py:14,26-31):
   ``iw = (min(ax2, bx2) - max(ax1, bx1)) + 1``, ``ih`` likewise, ``inter = iw * ih``, ``area = ((x2 - x1) + 1) * ((y2 - y1) +
   1)``, ``overlap = inter / ((area_a + area_b) - inter)``.  A non-positive ``iw`` or ``ih`` gives 0.
 
@@ -71,6 +71,8 @@ Limits: ``MAX_GT = 4096`` ground truths in one image (one taken-bit each in the 
 kernel being sized for the loop's 100.  Exceeding a limit is a ``ValueError``.
 """
 import numpy as np
+
+from .packing import cat, offsets, overlap_plus1
 
 MAX_GT = 4096                # ground truths of one image (csrc/image_relations.hip IR_MAXG)
 MAX_K = 8                    # values of K in one evaluation
@@ -187,33 +189,16 @@ def pack(relations, annotations, n_rel, nreturns=(50, 100), k_per_pair=None, see
         p_trip.append(got[0]), p_box.append(got[1]), p_conf.append(got[2]), p_row.append(got[3])
         p_n.append(len(got[0]))
         before.append(got[4])
-    cat = lambda xs, shape, dt: np.ascontiguousarray(np.concatenate(xs).astype(dt).reshape((-1,) + shape[1:])) if xs else np.zeros(shape, dt)
-    if sum(p_n) >= 2 ** 31 or sum(g_n) >= 2 ** 31:
-        raise ValueError("image_relations.pack: too many rows")
-    pred_off, gt_off = np.zeros(len(keys) + 1, np.int32), np.zeros(len(keys) + 1, np.int32)
-    np.cumsum(np.asarray(p_n, np.int64), out=pred_off[1:])
-    np.cumsum(np.asarray(g_n, np.int64), out=gt_off[1:])
+    pred_off, gt_off = (offsets(n, "image_relations.pack: too many rows") for n in (p_n, g_n))
     return Packed(keys=keys, n_ignored=n_ignored, n_rel=n_rel, max_pred=max_pred, pred_off=pred_off, gt_off=gt_off,
-                  pred_trip=cat(p_trip, (0, 3), np.int32), pred_box=cat(p_box, (0, 8), np.float64), pred_conf=cat(p_conf, (0,), np.float32),
-                  pred_row=cat(p_row, (0,), np.int32), n_before_cut=np.asarray(before, np.int32),
-                  gt_trip=cat(g_trip, (0, 3), np.int32), gt_box=cat(g_box, (0, 8), np.float64), gt_zs=cat(g_zs, (0,), np.int32))
+                  pred_trip=cat(p_trip, (3,), np.int32), pred_box=cat(p_box, (8,), np.float64), pred_conf=cat(p_conf, (), np.float32),
+                  pred_row=cat(p_row, (), np.int32), n_before_cut=np.asarray(before, np.int32),
+                  gt_trip=cat(g_trip, (3,), np.int32), gt_box=cat(g_box, (8,), np.float64), gt_zs=cat(g_zs, (), np.int32))
 
 
 # ------------------------------------------------------------------------------------------------------------------
 # host form
 # ------------------------------------------------------------------------------------------------------------------
-def _overlap(a, b):
-    """(n, 4) against (m, 4) float64 boxes -> (n, m), in the operation order of ``seqnms._overlap``."""
-    iw = (np.minimum(a[:, None, 2], b[None, :, 2]) - np.maximum(a[:, None, 0], b[None, :, 0])) + 1.0
-    ih = (np.minimum(a[:, None, 3], b[None, :, 3]) - np.maximum(a[:, None, 1], b[None, :, 1])) + 1.0
-    inter = iw * ih
-    aa = ((a[:, 2] - a[:, 0]) + 1.0) * ((a[:, 3] - a[:, 1]) + 1.0)
-    ab = ((b[:, 2] - b[:, 0]) + 1.0) * ((b[:, 3] - b[:, 1]) + 1.0)
-    with np.errstate(divide="ignore", invalid="ignore"):
-        ov = inter / ((aa[:, None] + ab[None, :]) - inter)
-    return np.where((iw <= 0.0) | (ih <= 0.0), 0.0, ov)
-
-
 def _union(box8):
     return np.stack([np.minimum(box8[:, 0], box8[:, 4]), np.minimum(box8[:, 1], box8[:, 5]),
                      np.maximum(box8[:, 2], box8[:, 6]), np.maximum(box8[:, 3], box8[:, 7])], 1)
@@ -222,8 +207,8 @@ def _union(box8):
 def scores_host(pred_trip, pred_box, gt_trip, gt_box):
     """(2, n_pred, n_gt) float64: ``ov`` of one image in relation and in phrase mode, -1 where the triplets differ."""
     same = (pred_trip[:, None, :] == gt_trip[None, :, :]).all(2)
-    rel = np.minimum(_overlap(pred_box[:, :4], gt_box[:, :4]), _overlap(pred_box[:, 4:], gt_box[:, 4:]))
-    phr = _overlap(_union(pred_box), _union(gt_box))
+    rel = np.minimum(overlap_plus1(pred_box[:, :4], gt_box[:, :4]), overlap_plus1(pred_box[:, 4:], gt_box[:, 4:]))
+    phr = overlap_plus1(_union(pred_box), _union(gt_box))
     return np.stack([np.where(same, rel, -1.0), np.where(same, phr, -1.0)])
 
 

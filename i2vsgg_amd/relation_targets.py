@@ -17,7 +17,7 @@ to the frame) and predicate; ``u`` (N_r, 10) uint32; ``ih``, ``iw`` (F) float64.
   to ``[0, w] x [0, h]``; the kept boxes are multiplied by the scale.  A frame keeps at most ``CAP = 64`` detections: the 64
   best by score (equal scores: the lower row), left in row order -- lane a of the kernel is detection a, as in Seq-NMS.
 * Match.  The overlap is float64 in the +1 convention of lib/model/nms/nms_cpu.py:14,26-31, in the operation order of
-  ``seqnms._overlap``.  Detection a matches annotated box g when the classes are equal and ``overlap >= 0.5``.
+  ``packing.overlap_plus1``.  Detection a matches annotated box g when the classes are equal and ``overlap >= 0.5``.
 * Candidates of the annotated relation (gs, go, r): every (a, b) with a matching gs, b matching go and a != b, a-major,
   ascending.  The integer weight of a candidate is ``floor((overlap(a, gs) * overlap(b, go)) * 65536.0)``: at least 16384,
   never 0, and within 2^-14 (relative) of the reference's weight.
@@ -47,7 +47,7 @@ int32; ``samp`` (N_r, 10, 2) int32, -1 where there is no draw; ``status``.
 """
 import numpy as np
 
-from .seqnms import _overlap
+from .packing import cat, overlap_plus1
 
 CAP = 64                     # detections of one frame (csrc/relation_targets.hip RT_CAP)
 P = 64                       # pair rows per frame
@@ -121,16 +121,15 @@ def pack(dets, annos, im_info, n_rel, u=None, names=None):
         det_box.append(k); det_cls.append(dc[keep]); kept.append(keep)
         gt_box.append(gb * sc); gt_cls.append(gc); rel.append(rl)
         det_off.append(det_off[-1] + len(keep)); gt_off.append(gt_off[-1] + len(gb)); rel_off.append(rel_off[-1] + len(rl))
-    cat = lambda parts, shape, dt: np.ascontiguousarray((np.concatenate(parts) if parts else np.zeros(0)).astype(dt).reshape(shape))
     n_r = rel_off[-1]
     if u is None:
         u = draw_uniforms(n_r)
     u = np.ascontiguousarray(u, np.uint32)
     if u.shape != (n_r, DRAWS):
         raise ValueError("relation_targets.pack: u is %r, the minibatch has %d relations: (%d, %d) wanted" % (u.shape, n_r, n_r, DRAWS))
-    pk = Packed(det_off=np.asarray(det_off, np.int32), det_box=cat(det_box, (-1, 4), np.float64), det_cls=cat(det_cls, (-1,), np.int32),
-                gt_off=np.asarray(gt_off, np.int32), gt_box=cat(gt_box, (-1, 4), np.float64), gt_cls=cat(gt_cls, (-1,), np.int32),
-                rel_off=np.asarray(rel_off, np.int32), rel=cat(rel, (-1, 3), np.int32), u=u,
+    pk = Packed(det_off=np.asarray(det_off, np.int32), det_box=cat(det_box, (4,), np.float64), det_cls=cat(det_cls, (), np.int32),
+                gt_off=np.asarray(gt_off, np.int32), gt_box=cat(gt_box, (4,), np.float64), gt_cls=cat(gt_cls, (), np.int32),
+                rel_off=np.asarray(rel_off, np.int32), rel=cat(rel, (3,), np.int32), u=u,
                 ih=np.ascontiguousarray(info[:, 0]), iw=np.ascontiguousarray(info[:, 1]), kept=kept)
     pk.boxes5 = box_table(pk)
     return pk
@@ -204,7 +203,7 @@ def relation_targets_host(det_off, det_box, det_cls, gt_off, gt_box, gt_cls, rel
         db = det_box[d0:d1]
         if d1 == d0 or g1 == g0:
             continue
-        ov = _overlap(db, gt_box[g0:g1])
+        ov = overlap_plus1(db, gt_box[g0:g1])
         match = (det_cls[d0:d1, None] == gt_cls[None, g0:g1]) & (ov >= 0.5)
         index, labels = {}, []
         for r in range(int(rel_off[f]), int(rel_off[f + 1])):

@@ -12,7 +12,7 @@ boxes of the class is present with zero boxes).
   earlier row), in their original row order; the rows beyond come back as suppressed.
 * Arithmetic.  Boxes and scores are float32 and are widened to float64 exactly; everything that decides something is float64
   in the order written here.
-* Overlap, the +1 convention of lib/model/nms/nms_cpu.py:14,26-27: ``iw = (min(x2) - max(x1)) + 1``, ``ih`` likewise; 0 if
+* Overlap (``packing.overlap_plus1``), the +1 convention of lib/model/nms/nms_cpu.py:14,26-27: ``iw = (min(x2) - max(x1)) + 1``, ``ih`` likewise; 0 if
   either is ``<= 0``, else ``iw*ih / ((area_a + area_b) - iw*ih)`` with ``area = ((x2 - x1) + 1) * ((y2 - y1) + 1)``.
 * Links.  Box a of frame t links to box b of frame t+1 when ``frame_no[t+1] == frame_no[t] + 1`` (a gap in the numbers
   breaks every link) and ``overlap >= link_iou``.
@@ -30,6 +30,8 @@ After a path that spans frames ts..te only frames <= te can change, and below ts
 unchanged ends the recomputation (frame t reads only frame t+1): both forms use this, it changes no result.
 """
 import numpy as np
+
+from .packing import cat, offsets, overlap_plus1
 
 CAP = 64                     # boxes of one frame that take part in a group (csrc/seqnms.hip SQ_CAP)
 RESCORE = ("avg", "max")
@@ -83,26 +85,10 @@ def pack(all_boxes, frame_index, score_thresh=0.0):
                 score.append(c[keep, 4])
                 row.append(keep)
             group_off.append(len(frame_no))
-    box_off = np.zeros(len(counts) + 1, np.int64)
-    np.cumsum(np.asarray(counts, np.int64), out=box_off[1:])
-    if box_off[-1] >= 2 ** 31:
-        raise ValueError("seqnms.pack: more than 2^31 boxes")
-    cat = lambda parts, shape, dt: (np.concatenate(parts) if parts else np.zeros(0)).astype(dt).reshape(shape)
-    return Packed(list(videos), n_classes, np.asarray(group_off, np.int32), np.asarray(frame_no, np.int32), box_off.astype(np.int32),
-                  np.ascontiguousarray(cat(box, (-1, 4), np.float32)), np.ascontiguousarray(cat(score, (-1,), np.float32)),
-                  np.asarray(slot_image, np.int64), cat(row, (-1,), np.int64), cell_rows)
-
-
-def _overlap(a, b):
-    """(n, 4) against (m, 4) float64 boxes -> (n, m), in the operation order of the module docstring."""
-    iw = (np.minimum(a[:, None, 2], b[None, :, 2]) - np.maximum(a[:, None, 0], b[None, :, 0])) + 1.0
-    ih = (np.minimum(a[:, None, 3], b[None, :, 3]) - np.maximum(a[:, None, 1], b[None, :, 1])) + 1.0
-    inter = iw * ih
-    aa = ((a[:, 2] - a[:, 0]) + 1.0) * ((a[:, 3] - a[:, 1]) + 1.0)
-    ab = ((b[:, 2] - b[:, 0]) + 1.0) * ((b[:, 3] - b[:, 1]) + 1.0)
-    with np.errstate(divide="ignore", invalid="ignore"):
-        ov = inter / ((aa[:, None] + ab[None, :]) - inter)
-    return np.where((iw <= 0.0) | (ih <= 0.0), 0.0, ov)
+    box_off = offsets(counts, "seqnms.pack: more than 2^31 boxes")
+    return Packed(list(videos), n_classes, np.asarray(group_off, np.int32), np.asarray(frame_no, np.int32), box_off,
+                  cat(box, (4,), np.float32), cat(score, (), np.float32), np.asarray(slot_image, np.int64),
+                  cat(row, (), np.int64), cell_rows)
 
 
 def _group_host(frame_no, B, S32, link_iou, nms_iou, rescore):
@@ -114,7 +100,7 @@ def _group_host(frame_no, B, S32, link_iou, nms_iou, rescore):
     link = [None] * nf
     for t in range(nf - 1):
         if int(frame_no[t + 1]) == int(frame_no[t]) + 1 and cnt[t] and cnt[t + 1]:
-            link[t] = _overlap(B[t], B[t + 1]) >= link_iou
+            link[t] = overlap_plus1(B[t], B[t + 1]) >= link_iou
     alive = [np.ones(n, bool) for n in cnt]
     best = [np.zeros(n) for n in cnt]
     ptr = [np.full(n, -1, np.int64) for n in cnt]
@@ -149,7 +135,7 @@ def _group_host(frame_no, B, S32, link_iou, nms_iou, rescore):
         while True:
             path.append((t, a))
             al = alive[t]
-            kill = al &(_overlap(B[t][a:a + 1], B[t])[0] > nms_iou)
+            kill = al &(overlap_plus1(B[t][a:a + 1], B[t])[0] > nms_iou)
             kill[a] = True
             alive[t] = al & ~kill
             nx = int(ptr[t][a])

@@ -13,6 +13,8 @@ and the gather, and both do their arithmetic in float64 in the same operation or
 """
 import numpy as np
 
+from .packing import cat, offsets
+
 MAX_PER_FRAME = 100          # predictions of one frame that take part
 MAX_PER_VIDEO = 200          # relations kept per video
 MIN_MEMBERS = 10             # a relation seen on fewer frames is dropped
@@ -113,8 +115,7 @@ def pack_frames(frame_relations):
                 boxes.append(list(p[2][0]) + list(p[2][1]))
                 idex.append(p[3])
         frame_off.append(len(frame_no))
-    pred_off = np.zeros(len(counts) + 1, np.int32)
-    np.cumsum(np.asarray(counts, np.int64), out=pred_off[1:])
+    pred_off = offsets(counts, "video.pack_frames: more than 2^31 predictions")
     rel_idex = np.empty(len(idex), object)
     rel_idex[:] = idex
     return Packed(vids, np.asarray(frame_off, np.int32), np.asarray(frame_no, np.int32), pred_off,
@@ -310,10 +311,8 @@ def pack_eval(prediction, groundtruth):
         score.extend(float(r["score"]) for r in preds)
         pred_off.append(pred_off[-1] + len(preds))
         gt_off.append(gt_off[-1] + len(gts))
-    cat = lambda parts, shape: np.concatenate(parts) if parts else np.zeros(shape)
-    return PackedEval(vids, np.asarray(pred_off, np.int32), cat(pred_rel, (0, REL_COLS)).astype(np.int32),
-                      np.asarray(score, np.float64), np.asarray(gt_off, np.int32), cat(gt_rel, (0, REL_COLS)).astype(np.int32),
-                      cat(boxes, (0, 4)).astype(np.float64))
+    return PackedEval(vids, np.asarray(pred_off, np.int32), cat(pred_rel, (REL_COLS,), np.int32), np.asarray(score, np.float64),
+                      np.asarray(gt_off, np.int32), cat(gt_rel, (REL_COLS,), np.int32), cat(boxes, (4,), np.float64))
 
 
 def _viou(pr, gr, c, boxes, vol_p, vol_g):
