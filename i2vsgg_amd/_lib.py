@@ -109,6 +109,8 @@ SIGNATURES = {
     "i2v_det_eval_match": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, C.c_double, _p, _p, _p, _p, _z, _p]),
     "i2v_det_eval_curve_workspace_bytes": (_z, [_i]),
     "i2v_det_eval_curve": (_i, [_p, _p, _p, _p, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _z, _p]),
+    "i2v_proposal_cover_workspace_bytes": (_z, [_i]),
+    "i2v_proposal_cover": (_i, [_p] * 7 + [_i] * 7 + [_p, _p, _p, _p, _z, _p]),
     "i2v_image_prep_size": (_i, [_i, _i, _i, _p, _p, _p]),
     "i2v_image_prep": (_i, [_p, _i, _i, _i, _i, _p, _i, _p, _i, _i, _p]),
     "i2v_det_postprocess_workspace_bytes": (_z, [_i, _i]),

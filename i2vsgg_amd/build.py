@@ -8,7 +8,7 @@ CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libi2vsgg_hip.so")
 SOURCES = ["api.cpp", "roi_ops.hip", "rpn.hip", "conv.hip", "wgrad.hip", "elementwise.hip", "heads.hip", "image.hip", "winograd.hip",
            "dstyle.hip", "video.hip", "det_eval.hip", "seqnms.hip", "recognition.hip", "relation_targets.hip",
-           "image_relations.hip", "relation_features.hip"]
+           "image_relations.hip", "relation_features.hip", "proposal_eval.hip"]
 # -ffp-contract=off: box / IoU / ROIAlign arithmetic must round once per operation like the
 # reference's CPU path (no FMA contraction), or NMS threshold decisions can flip.
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-ffp-contract=off", "-fno-fast-math",

@@ -11,6 +11,7 @@
                   branch of ``forward_predicate`` returns (numpy, the host form); ``ops.recognition_rows`` is its device form.
 ``recognition_frame``  backbone forward + ``forward_predicate_eval`` + the device form of that tail for one frame.
 ``DetectStep``    ``detect_frame`` for several frames at a time as one replayable HIP graph (a branch per frame).
+``trim_proposals``  the RPN's proposals of a frame without the proposal layer's padding rows (``keep_proposals`` of the two above).
 ``RelationStep``  ``relation_frame`` + ``detection_output`` the same way.
 ``keeping_relation_features``  a ``with`` block inside which ``relation_frame`` and every ``RelationStep`` built also hand the relation
                   head's per-pair feature (``pre_feat``) to a sink (``relation_features.ArenaSink``), on the device.
@@ -163,10 +164,17 @@ class DetectStep(_FrameGraphStep):
     ``step(im_data, im_info)`` -> list over the frames of the reference's ``all_boxes[j][i]`` lists; ``step.run(batches)``
     keeps one batch in flight while the host unpacks the previous one.  Frames of one call share a size (the loader pads a
     minibatch to one size).  The frame's ``im_info`` row is read on the device (``i2v_det_postprocess_info``), so frames of
-    any scale replay the same graph."""
+    any scale replay the same graph.
+
+    ``keep_proposals=True`` also keeps what the RPN proposed: the captured body copies ``rois[0]`` of each frame into a static
+    buffer ``props (frames, R, 5)`` of its own, ``launch()`` queues that buffer's copy into the alternating pinned slots behind
+    the detections', and ``collect()`` returns ``(results, proposals)``: next to today's list, per frame the (n, 4) float32
+    proposals in scaled-image coordinates, best first, without the zero rows the proposal layer pads with
+    (``trim_proposals``).  With the default ``False`` no buffer, copy or graph node is added and ``collect()`` returns what it
+    returns today."""
 
     def __init__(self, net, frames=2, thresh=0.0, max_per_image=100, class_agnostic=False, device="cuda:0", use_graph=True,
-                 max_graphs=8):
+                 max_graphs=8, keep_proposals=False):
         super().__init__(net, frames, device, use_graph, max_graphs)
         self.thresh, self.max_per_image, self.class_agnostic = float(thresh), int(max_per_image), bool(class_agnostic)
         self.R, self.C = int(cfg.TEST.RPN_POST_NMS_TOP_N), int(net.n_classes)
@@ -175,11 +183,17 @@ class DetectStep(_FrameGraphStep):
         self.counts = torch.zeros((self.frames, self.C), device=self.dev, dtype=torch.int32)
         self._host = [(torch.zeros(self.dets.shape).pin_memory(), torch.zeros(self.counts.shape, dtype=torch.int32).pin_memory(),
                        torch.cuda.Event()) for _ in range(2)]
+        self.keep_proposals, self.props, self._props_host = bool(keep_proposals), None, None
+        if self.keep_proposals:
+            self.props = torch.zeros((self.frames, self.R, 5), device=self.dev)
+            self._props_host = [torch.zeros(self.props.shape).pin_memory() for _ in range(2)]
 
     def _frame(self, fs, f):
         """One frame, as the reference's loop body runs it."""
         with fs.ctx[f]:
             rois, cls_prob, bbox_pred = self.net.forward_detect(fs.im[f:f + 1], self.info[f:f + 1])
+            if self.keep_proposals:
+                self.props[f].copy_(rois[0])
             stds = means = None
             agnostic = self.class_agnostic
             if cfg.TEST.BBOX_REG and cfg.TRAIN.BBOX_NORMALIZE_TARGETS_PRECOMPUTED:
@@ -222,15 +236,22 @@ class DetectStep(_FrameGraphStep):
         dets_h, counts_h, ev = self._host[self._slot]
         dets_h.copy_(self.dets, non_blocking=True)
         counts_h.copy_(self.counts, non_blocking=True)
+        props_h = None
+        if self.keep_proposals:                                  # ahead of the event: one wait covers the three copies
+            props_h = self._props_host[self._slot]
+            props_h.copy_(self.props, non_blocking=True)
         ev.record(torch.cuda.current_stream(self.dev))
         self._slot ^= 1
-        return (dets_h, counts_h, ev, self._n)
+        return (dets_h, counts_h, ev, self._n) if props_h is None else (dets_h, counts_h, ev, self._n, props_h)
 
     def collect(self, token):
-        dets_h, counts_h, ev, n = token
+        dets_h, counts_h, ev, n = token[:4]
         ev.synchronize()
         dets, counts = dets_h.numpy(), counts_h.numpy()
-        return [[np.array(dets[f, j, :counts[f, j]]) for j in range(self.C)] for f in range(n)]
+        res = [[np.array(dets[f, j, :counts[f, j]]) for j in range(self.C)] for f in range(n)]
+        if len(token) == 4:
+            return res
+        return res, [trim_proposals(token[4].numpy()[f]) for f in range(n)]
 
 
 class RelationStep(_FrameGraphStep):
@@ -377,10 +398,22 @@ class RelationStep(_FrameGraphStep):
         return res
 
 
+def trim_proposals(rois):
+    """(R, 5) rows of [batch index, x1, y1, x2, y2] as the proposal layer leaves them -> the (n, 4) float32 proposals: the
+    zero rows it pads a short list with (proposal_layer.py:157-161) are dropped from the end -- the trailing rows whose four
+    coordinates are all 0."""
+    boxes = np.array(np.asarray(rois, np.float32).reshape(-1, 5)[:, 1:5])
+    real = np.flatnonzero((boxes != 0).any(axis=1))
+    return np.ascontiguousarray(boxes[:real[-1] + 1 if len(real) else 0])
+
+
 @torch.no_grad()
-def detect_frame(net, im_data, im_info, gt_boxes, num_boxes, thresh=0.0, max_per_image=100, class_agnostic=False):
+def detect_frame(net, im_data, im_info, gt_boxes, num_boxes, thresh=0.0, max_per_image=100, class_agnostic=False,
+                 keep_proposals=False):
     """Returns ``all_boxes_i``: list over classes of (n_j, 5) float32 arrays [x1,y1,x2,y2,score] in original-image
-    coordinates (entry 0, background, is empty) -- the reference's ``all_boxes[j][i]`` for this frame."""
+    coordinates (entry 0, background, is empty) -- the reference's ``all_boxes[j][i]`` for this frame.  ``keep_proposals``:
+    returns ``(all_boxes_i, proposals)``, the second the frame's (n, 4) float32 proposals in scaled-image coordinates
+    (``trim_proposals`` of ``rois``)."""
     assert im_data.shape[0] == 1, "the reference evaluates one frame at a time (test_net_...:95 batch_size 1)"
     if hasattr(net, "forward_detect") and not net.training:
         out = net.forward_detect(im_data, im_info)        # the three outputs read below; the discriminators' are not computed
@@ -399,7 +432,10 @@ def detect_frame(net, im_data, im_info, gt_boxes, num_boxes, thresh=0.0, max_per
                                              thresh, cfg.TEST.NMS, max_per_image)
     counts = counts.cpu().numpy()                  # the one synchronisation of the frame
     dets = dets.cpu().numpy()
-    return [np.ascontiguousarray(dets[j, :counts[j]]) for j in range(C)]
+    res = [np.ascontiguousarray(dets[j, :counts[j]]) for j in range(C)]
+    if keep_proposals:
+        return res, trim_proposals(rois.reshape(-1, 5).cpu().numpy())
+    return res
 
 
 def detection_output(vrd_data, k=100):

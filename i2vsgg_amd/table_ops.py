@@ -1,5 +1,6 @@
 """torch-facing wrappers of the packed-table ops: the evaluation and target kernels that read flat arrays and offset tables
-(csrc/seqnms.hip, video.hip, det_eval.hip, recognition.hip, relation_features.hip, relation_targets.hip, image_relations.hip;
+(csrc/seqnms.hip, video.hip, det_eval.hip, recognition.hip, relation_features.hip, relation_targets.hip, image_relations.hip,
+proposal_eval.hip;
 csrc/table_common.h is what those share, ``packing.py`` what their host packers share).  ``ops`` re-exports the public names.
 
 Every op takes arrays or tensors, stages them on the device, launches on torch's current stream and, unless it says
@@ -347,3 +348,39 @@ def det_eval_curve(det_key, cls_off, flag, npos, device=None):
     if C > 0:
         _status(ws, 0, "det_eval_curve", "class")
     return perm, cum_tp, cum_fp, rec, prec, ap_area, ap_11pt
+
+
+def proposal_cover(cand_off, cand_box, gt_off, gt_box, gt_area, limits, ranges, device=None, out=None):
+    """The greedy cover of every (image, limit, area range) cell, one workgroup per cell (include/i2vsgg_hip.h,
+    i2v_proposal_cover; ``proposal_eval.pack`` builds the arrays).  Arrays or tensors: cand_off, gt_off (I+1), limits (L) int32;
+    cand_box (N,4), gt_box (G,4), gt_area (G), ranges (A,2) fp64.  Returns device tensors (ov (L,A,G) fp64, cand (L,A,G) int32,
+    step (L,A,G) int32), -1 where a ground truth lies outside the range.  ``out``: three such tensors to write into instead
+    (an image with malformed tables leaves its entries as they were)."""
+    dev = _device(device, "proposal_eval.cover_arrays_host")
+    if (np.asarray(torch.as_tensor(limits).cpu()).reshape(-1) < 1).any():
+        raise ValueError("proposal_cover: every limit is >= 1 (2^31 - 1: no limit)")
+    max_cand, max_gt = max(_max_rows(cand_off), 0), max(_max_rows(gt_off), 0)
+    cand_off, gt_off, limits = (t.reshape(-1) for t in _stage(dev, torch.int32, cand_off, gt_off, limits))
+    cand_box, gt_box, gt_area, ranges = _stage(dev, torch.float64, cand_box, gt_box, gt_area, ranges)
+    I, N, G, L, A = cand_off.numel() - 1, cand_box.numel() // 4, gt_area.numel(), limits.numel(), ranges.numel() // 2
+    if I < 0 or gt_off.numel() != I + 1 or cand_box.numel() != 4 * N or gt_box.numel() != 4 * G or ranges.numel() != 2 * A:
+        raise ValueError("proposal_cover: array sizes do not agree")
+    if not 1 <= L <= 8 or not 1 <= A <= 8:
+        raise ValueError("proposal_cover: 1 to 8 limits and 1 to 8 area ranges (got %d and %d)" % (L, A))
+    if out is None:
+        ov = torch.full((L, A, G), -1.0, device=dev, dtype=torch.float64)
+        cand = torch.full((L, A, G), -1, device=dev, dtype=torch.int32)
+        step = torch.full((L, A, G), -1, device=dev, dtype=torch.int32)
+    else:
+        ov, cand, step = out
+        for t, dt in ((ov, torch.float64), (cand, torch.int32), (step, torch.int32)):
+            if t.device != dev or t.dtype != dt or tuple(t.shape) != (L, A, G) or not t.is_contiguous():
+                raise ValueError("proposal_cover: out is (ov fp64, cand int32, step int32), each (%d, %d, %d) on %s" % (L, A, G, dev))
+    # the caps are the kernel's to refuse, image by image (status word): what it sizes its LDS by stays inside them
+    ws = _launch(dev, "proposal_cover", lambda *tail: lib.i2v_proposal_cover(
+        ptr(cand_off), ptr(cand_box), ptr(gt_off), ptr(gt_box), ptr(gt_area), ptr(limits), ptr(ranges), I, N, G, L, A,
+        min(max_gt, 4096), min(max_cand, 65535), ptr(ov), ptr(cand), ptr(step), *tail), lib.i2v_proposal_cover_workspace_bytes(I),
+        "proposal_eval")
+    if I > 0:
+        _status(ws, 0, "proposal_cover", "image", "the offset tables are out of range or over a cap at")
+    return ov, cand, step

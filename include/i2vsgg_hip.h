@@ -431,6 +431,28 @@ int32_t i2v_det_eval_curve(const int32_t* det_key, const int32_t* cls_off, const
                            double* rec, double* prec, double* ap_area, double* ap_11pt,
                            void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- proposal / detection recall: the greedy cover of every (image, limit, area range) cell -----------------------
+ * The rules are stated in full in i2vsgg_amd/proposal_eval.py, whose pack() builds the tables.  Image i owns the candidates
+ * [cand_off[i], cand_off[i+1]) of cand_box (n_cand x 4 fp64, rank order, best first; at most max_cand <= 65535 in one
+ * image) and the ground truths [gt_off[i], gt_off[i+1]) of gt_box (n_gt x 4 fp64) / gt_area (n_gt fp64), at most max_gt <=
+ * 4096 in one image; limits (n_limits int32, 1 to 8, each >= 1; 2^31 - 1: no limit) and ranges (n_areas x 2 fp64, 1 to 8,
+ * inclusive bounds on gt_area) are device arrays too.  One workgroup per cell (i, l, a): its candidates are the image's first
+ * min(n, limits[l]) rows, its ground truths those with ranges[a][0] <= area <= ranges[a][1], in table order.  As often as it
+ * has ground truths: among those still free the largest +1-convention overlap (fp64, i2v_overlap_plus1's operation order)
+ * with a candidate still free, ties to the lowest ground truth, then to the lowest candidate; both retire.  ov, cand, step
+ * (n_limits x n_areas x n_gt; fp64, int32, int32) receive, at [l][a][the ground truth's row], that overlap, the candidate's
+ * index within the image and the step number; once no candidate is free the remaining ground truths receive 0, -1 and the
+ * step numbers that follow, in ascending row; a ground truth outside the range receives -1, -1, -1.  No overlap matrix is
+ * kept: a cell's state is 14 bytes per ground truth and one bit per candidate in LDS (65 544 bytes at both caps: more than 64 KB, inside the 160 KB of a gfx950 workgroup).  No floating-point atomics: two runs
+ * give the same bits.  The first int32 of the workspace is a status word: 0, or 1 + the largest index of an image whose
+ * cand_off / gt_off entries are not monotone, leave the tables or exceed max_cand / max_gt; nothing is written for such an
+ * image. */
+size_t  i2v_proposal_cover_workspace_bytes(int32_t n_images);
+int32_t i2v_proposal_cover(const int32_t* cand_off, const double* cand_box, const int32_t* gt_off, const double* gt_box,
+                           const double* gt_area, const int32_t* limits, const double* ranges, int32_t n_images,
+                           int32_t n_cand, int32_t n_gt, int32_t n_limits, int32_t n_areas, int32_t max_gt, int32_t max_cand,
+                           double* ov, int32_t* cand, int32_t* step, void* workspace, size_t workspace_bytes, void* stream);
+
 /* IoU of boxes (B,N,4 | stride_box floats per row, first 4 used after `box_off`) against
  * gt (B,K,5): bbox_transform.py:168-257 (bbox_overlaps_batch) incl. the zero-area
  * masks; also emits per-row max/argmax (first max).  overlaps may be NULL. */
