@@ -51,6 +51,13 @@ def _cell(c):
     return np.asarray(c, np.float32).reshape(-1, 5)
 
 
+def frame_index_of_paths(paths, frames_per_video=0):
+    """{path: (vid, fno)} for an imdb without video ids, the one rule of the command-line tools: the frames in the order of
+    their paths, every ``frames_per_video`` consecutive ones a video "0", "1", ... numbered from 0 (0 or less: one video)."""
+    per = frames_per_video if frames_per_video > 0 else max(len(paths), 1)
+    return dict((path, (str(k // per), k % per)) for k, path in enumerate(sorted(paths)))
+
+
 def pack(all_boxes, frame_index, score_thresh=0.0):
     """``all_boxes[j][i]``: (n, 5) float32 rows [x1, y1, x2, y2, score] of class j in image i (the nested list that
     ``test_instance_styled.py`` pickles; an empty cell may be ``[]``).  ``frame_index[i] = (vid, fno)``.  Rows with

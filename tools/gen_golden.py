@@ -1240,13 +1240,88 @@ def gen_video_relation_feat():
     save("video_relation_feat", "extracted", n_cases=np.array(len(cases.golden_inputs())), **out)
 
 
+# ----------------------------------------------------------------------------- trajectory mAP of object tracks
+def gen_track_eval():
+    """tests/golden/track_eval.npz: the reference's eval_detection_scores / viou on the gap-free cases of
+    tests/track_eval_cases.py golden_case.  Every trajectory enters as a relation with ``triplet = (class,)`` and ``sub_traj =
+    obj_traj =`` the trajectory, so ``min(s_iou, o_iou)`` is the single vIoU and the reference's greedy loop is the matching of
+    i2vsgg_amd.track_eval.  Per case: the seed it ended on, per threshold which predictions (packed order) hit and with what
+    ov, and the smallest margins.  The reference adds in list order, the package in its lane order: a float32 case with a
+    decision closer than 1e-9 (relative) to a threshold or a rival ov is redrawn from the next seed -- never dropped; the
+    integer cases are exact in any order and keep their ties."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import track_eval_cases as tc
+    from i2vsgg_amd import track_eval
+    MARGIN = 1e-9
+    ns = _utils_functions(["viou", "eval_detection_scores"])
+    ref_viou = ns["viou"]
+    calls = []
+    ns["viou"] = lambda t1, d1, t2, d2: calls.append((id(t1), ref_viou(t1, d1, t2, d2))) or calls[-1][1]
+    thr = list(tc.THRESHOLDS)
+    seeds, off, hits, ovs, m_ov, m_gap, redraws = [], [0], [], [], [], [], 0
+    for k in range(tc.GOLDEN_CASES):
+        integer = k % 2 == 0
+        seed = tc.GOLDEN_SEED + 100 * k
+        while True:
+            prediction, groundtruth = tc.golden_case(seed, integer)
+            st = {}
+            pk, _, ov_h, hit_h, hit_ov_h = track_eval.match(prediction, groundtruth, thr, stats=st)
+            if integer or min(st.get("ov", np.inf), st.get("ov_gap", np.inf)) >= MARGIN:
+                break
+            seed, redraws = seed + 1, redraws + 1
+        rel = lambda tr, score=None: dict(
+            triplet=(tr["category"],), duration=[tr["frames"][0], tr["frames"][-1] + 1], score=score,
+            sub_traj=np.asarray(tr["boxes"], np.float64).tolist(), obj_traj=np.asarray(tr["boxes"], np.float64).tolist())
+        preds = [rel(tr, tr["score"]) for tr in prediction["g"]]
+        for r in preds:
+            r["obj_traj"] = r["sub_traj"]
+        gts = [rel(tr) for tr in groundtruth["g"]]
+        for r in gts:
+            r["obj_traj"] = r["sub_traj"]
+        order = np.argsort(-np.array([r["score"] for r in preds]), kind="stable")
+        pid = dict((id(r["sub_traj"]), i) for i, r in enumerate(preds))
+        hit_ref, ov_ref = np.zeros((len(thr), pk.n_pred), bool), np.full((len(thr), pk.n_pred), np.nan)
+        for t, th in enumerate(thr):
+            del calls[:]
+            _, _, hit_scores = ns["eval_detection_scores"](gts, preds, th)
+            tp = np.zeros(len(preds), bool)
+            tp[order] = np.isfinite(hit_scores)
+            best = np.full(len(preds), -np.inf)
+            for i, val in calls:                                 # a prediction's hit is its largest computed ov >= threshold
+                if val >= th:
+                    best[pid[i]] = max(best[pid[i]], val)
+            assert (np.isfinite(best) == tp).all()
+            hit_ref[t] = tp[pk.pred_src]
+            ov_ref[t] = np.where(tp, best, np.nan)[pk.pred_src]
+        # the package's host form must already agree
+        assert ((hit_h >= 0) == hit_ref).all(), k
+        assert np.allclose(hit_ov_h[hit_ref], ov_ref[hit_ref], rtol=1e-12, atol=0), k
+        if integer:
+            assert (hit_ov_h[hit_ref] == ov_ref[hit_ref]).all(), k
+        print("    case %2d seed %d (%s): %3d predictions, %3d ground truths, hits %s, margins ov %.3g gap %.3g" % (
+            k, seed, "integer" if integer else "float32", pk.n_pred, pk.n_gt, hit_ref.sum(1).tolist(), st.get("ov", np.inf),
+            st.get("ov_gap", np.inf)))
+        seeds.append(seed)
+        off.append(off[-1] + pk.n_pred)
+        hits.append(hit_ref)
+        ovs.append(ov_ref)
+        m_ov.append(st.get("ov", np.inf))
+        m_gap.append(st.get("ov_gap", np.inf))
+    hits, ovs = np.concatenate(hits, 1), np.concatenate(ovs, 1)
+    assert len(seeds) == tc.GOLDEN_CASES and hits[0].sum() > hits[1].sum() > hits[2].sum() > 0 and (~hits[0]).any()
+    assert np.isfinite(m_gap[1::2]).any() and np.isfinite(m_gap[0::2]).any()       # rival ground truths, float32 and integer
+    print("    %d redraws" % redraws)
+    save("track_eval", "extracted", seeds=np.asarray(seeds, np.int32), pred_off=np.asarray(off, np.int32), thresholds=np.asarray(thr),
+         hit=hits, hit_ov=ovs, margin_ov=np.asarray(m_ov), margin_ov_gap=np.asarray(m_gap), margin_bound=np.float64(MARGIN))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--only", default="")
     a = ap.parse_args()
     os.makedirs(GOLD, exist_ok=True)
     todo = a.only.split(",") if a.only else ["direct", "roialign", "roialign_fresh", "tails", "rpn", "nets", "full", "ctx", "step",
-                                             "vrd", "video", "det_eval", "recognition", "video_relation_feat"]
+                                             "vrd", "video", "det_eval", "recognition", "video_relation_feat", "track_eval"]
     if "direct" in todo:
         print("[direct imports]")
         gen_direct()
@@ -1277,6 +1352,9 @@ def main():
     if "video_relation_feat" in todo:
         print("[video relation features: generate_static_relation_feat of lib/utils.py compiled from its own lines]")
         gen_video_relation_feat()
+    if "track_eval" in todo:
+        print("[trajectory mAP of object tracks: viou / eval_detection_scores of lib/utils.py compiled from their own lines]")
+        gen_track_eval()
     if any(t in todo for t in ("rpn", "nets", "full", "vrd", "ctx", "step")):
         print("[imports with placeholders]")
         cfg = install_placeholders()

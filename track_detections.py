@@ -6,8 +6,11 @@ the relation test loop.  ``--detections`` is the ``detections.pkl`` that ``test_
 ``tracked_boxes.pkl``, {frame file name: {boxes, box_classes, scores, tids, rels: []}}, which ``test_sgg_emb.py`` /
 ``video_sgg_emb.py`` take as ``--target_gt_rels_path``.  Frames map to (video, frame number) as in ``video_sgg_emb.py``: the
 frames in the order of their paths, every ``--frames_per_video`` consecutive ones a video (default: one video).  The linking
-runs on the GPU; ``--cpu`` runs the same rules on the host."""
+runs on the GPU; ``--cpu`` runs the same rules on the host.  ``--save_tracks`` also writes ``tracks.json``, the tracks as
+trajectories, and ``--groundtruth FILE`` scores them right away (trajectory mAP, ``eval_tracks.py`` has the file formats); without
+the two options nothing else is written or printed."""
 import argparse
+import json
 import os
 import pickle
 import sys
@@ -32,6 +35,10 @@ def main(argv=None):
     p.add_argument("--min_len", type=int, default=1, help="tracked_boxes.pkl: members a track needs")
     p.add_argument("--cpu", action="store_true", help="host implementation (no GPU needed)")
     p.add_argument("--output_dir", default=None)
+    p.add_argument("--save_tracks", action="store_true", help="also write tracks.json: the tracks as trajectories (eval_tracks.py reads it)")
+    p.add_argument("--groundtruth", default=None, help="annotated trajectories (.json) or per-frame boxes with tids (.pkl): "
+                   "print the trajectory mAP of the tracks right after linking (i2vsgg_amd/track_eval.py)")
+    p.add_argument("--thresholds", nargs="+", type=float, default=[0.5, 0.7, 0.9], help="with --groundtruth: the vIoU thresholds")
     a = p.parse_args(argv)
     from i2vsgg_amd import seqnms
     from i2vsgg_amd.roi_data_layer.roidb import get_imdb
@@ -40,8 +47,7 @@ def main(argv=None):
     imdb = get_imdb(a.imdbval_name)
     n = len(all_boxes[0]) if len(all_boxes) else 0
     paths = [imdb.image_path_at(i) for i in range(n)]
-    per = a.frames_per_video if a.frames_per_video > 0 else max(n, 1)
-    index = dict((path, (str(k // per), k % per)) for k, path in enumerate(sorted(paths)))
+    index = seqnms.frame_index_of_paths(paths, a.frames_per_video)
     frame_index = [index[path] for path in paths]
     t0 = time.time()
     out, tracks = seqnms.seq_nms(all_boxes, frame_index, a.link_iou, a.nms_iou, a.rescore, a.score_thresh,
@@ -60,6 +66,17 @@ def main(argv=None):
         with open(os.path.join(out_dir, name), "wb") as f:
             pickle.dump(obj, f, pickle.HIGHEST_PROTOCOL)
         print("wrote %s" % os.path.join(out_dir, name))
+    if a.save_tracks or a.groundtruth:
+        from i2vsgg_amd import track_eval
+        trajs = track_eval.from_seq_nms(out, tracks, frame_index, a.min_len)
+        if a.save_tracks:
+            with open(os.path.join(out_dir, "tracks.json"), "w") as f:
+                json.dump(trajs, f)
+            print("wrote %s" % os.path.join(out_dir, "tracks.json"))
+        if a.groundtruth:
+            import eval_tracks
+            gts = eval_tracks.load_groundtruth(a.groundtruth, dict((path.split("/")[-1], v) for path, v in index.items()))
+            track_eval.report(track_eval.evaluate(trajs, gts, a.thresholds))       # host code, with or without --cpu
     return out, tracks, anno
 
 
