@@ -90,6 +90,8 @@ SIGNATURES = {
     "i2v_relation_topk": (_i, [_p, _p, _p, _p, _i, _i, _i, _p, _p, _p, _p, _z, _p]),
     "i2v_video_associate_workspace_bytes": (_z, [_i, _i, _i]),
     "i2v_video_associate": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _z, _p]),
+    "i2v_video_associate_tracks_workspace_bytes": (_z, [_i, _i, _i]),
+    "i2v_video_associate_tracks": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _z, _p]),
     "i2v_video_viou_match_workspace_bytes": (_z, [_i, _i]),
     "i2v_video_viou_match": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _l, _i, _i, C.c_double, _p, _p, _p, _p, _z, _p]),
     "i2v_seqnms_workspace_bytes": (_z, [_i, _i, _i]),

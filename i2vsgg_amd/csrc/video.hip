@@ -205,6 +205,224 @@ extern "C" int32_t i2v_video_associate(const int32_t* frame_off, const int32_t* 
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
+// Association along object tracks (the rules: i2vsgg_amd/video.py, associate_tracks)
+// ---------------------------------------------------------------------------------------------------------------------
+
+#define VT_MAXGAP 7                          // frames a relation may stay out of its frames' lists and still go on
+#define VT_CAP (VA_MAXP * (VT_MAXGAP + 1))   // open relations: last member within max_gap + 1 frame numbers, 100 per frame
+#define VT_PER 4                             // entries a thread moves when the table is compacted: 256 x 4 >= VT_CAP
+
+// One workgroup per video, persistent over its frames.  The open table holds at most one relation per key (a prediction
+// that opens a relation replaces the open one of its key), so a prediction has at most one entry to look at and the
+// table's order decides nothing.  Per frame: rank the predictions; find each one's entry; extend it in place or open a
+// relation; drop the entries no later frame can reach, stably; append the relations whose key had no entry.
+__global__ void __launch_bounds__(VA_THREADS)
+video_associate_tracks_kernel(const int* __restrict__ frame_off, const int* __restrict__ frame_no, const int* __restrict__ pred_off,
+                              const double* __restrict__ score, const int* __restrict__ key, const int* __restrict__ since,
+                              int n_frames, int n_preds, int max_gap, int* __restrict__ rel_id, int* __restrict__ rel_start,
+                              int* __restrict__ rel_end, int* __restrict__ rel_len, double* __restrict__ rel_score,
+                              int* __restrict__ n_rel, int* status) {
+    __shared__ double o_sum[VT_CAP];                     // the open relations: running sum of scores in member order,
+    __shared__ int o_key[3][VT_CAP];                     // key (subject object index, predicate, object object index),
+    __shared__ int o_last[VT_CAP], o_cnt[VT_CAP], o_id[VT_CAP];      // last member frame number, members, id
+    __shared__ double s_key[VA_MAXP];                    // the frame's scores as given
+    __shared__ double c_score[VA_MAXP];                  // the frame in descending score (stable)
+    __shared__ int c_key[VA_MAXP][3], c_since[VA_MAXP], c_src[VA_MAXP];
+    __shared__ int s_found[VA_MAXP][2];                  // the entry of the prediction's key in either half of the table, or -1
+    __shared__ int s_new[VA_MAXP], s_app[VA_MAXP];       // the prediction opens a relation / its key has no entry
+    __shared__ int s_wsum[VA_THREADS / 64];
+    __shared__ int s_dup;
+    const int v = blockIdx.x, t = threadIdx.x;
+    const int f0 = frame_off[v], f1 = frame_off[v + 1];
+    if (i2v_range_bad(f0, f1, n_frames)) {               // a malformed table: say so, touch nothing
+        if (t == 0) {
+            atomicMax(status, n_frames + 1);
+            n_rel[v] = 0;
+        }
+        return;
+    }
+    int base = 0;                                        // the video's relations live at [base, base + its predictions)
+    int next = 0, m = 0, prev_no = 0;
+    bool any = false;                                    // a frame number has been taken
+    for (int f = f0; f < f1; ++f) {
+        int p0 = pred_off[f];
+        int n = pred_off[f + 1] - p0;
+        const int fno = frame_no[f];
+        bool bad = n > VA_MAXP || i2v_span_bad(p0, n, n_preds);
+        if (bad) p0 = 0;
+        if (f == f0) base = p0;
+        if (any && fno <= prev_no) bad = true;           // frame numbers ascend strictly: the bound of the table rests on it
+        if (bad) n = 0;
+        // 1. the frame's predictions, in descending score (stable)
+        if (t == 0) s_dup = 0;
+        if (t < n) s_key[t] = score[p0 + t];
+        __syncthreads();
+        if (t < n) {
+            const int r = va_rank_desc(s_key, n, t);
+            c_score[r] = s_key[t];
+            c_src[r] = t;
+            for (int k = 0; k < 3; ++k) c_key[r][k] = key[(size_t)(p0 + t) * 3 + k];
+            c_since[r] = since[p0 + t];
+        }
+        __syncthreads();                                 // the ranked frame is written
+        if (t < n) {
+            for (int j = 0; j < t; ++j)
+                if (c_key[j][0] == c_key[t][0] && c_key[j][1] == c_key[t][1] && c_key[j][2] == c_key[t][2]) s_dup = 1;
+        }
+        __syncthreads();
+        if (s_dup) {                                     // a repeated key: no such frame comes from the packer
+            bad = true;
+            n = 0;
+        }
+        if (bad && t == 0) atomicMax(status, f + 1);     // the frame is skipped as if empty; the caller reads the status
+        // 2. the entry of every prediction's key: thread (p, h) looks through half h of the table
+        {
+            const int p = t & 127, h = t >> 7;
+            if (p < n) {
+                const int half = (m + 1) >> 1;
+                const int e1 = m < (h + 1) * half ? m : (h + 1) * half;
+                const int k0 = c_key[p][0], k1 = c_key[p][1], k2 = c_key[p][2];
+                int found = -1;
+                for (int e = h * half; e < e1; ++e)
+                    if (o_key[0][e] == k0 && o_key[1][e] == k1 && o_key[2][e] == k2) found = e;       // at most one
+                s_found[p][h] = found;
+            }
+        }
+        __syncthreads();                                 // matches found
+        // 3. extend or open
+        int e = -1;
+        bool ext = false;
+        if (t < n) {
+            e = s_found[t][0] >= 0 ? s_found[t][0] : s_found[t][1];
+            if (e >= 0) {
+                const long long d = (long long)fno - o_last[e];
+                ext = d >= 1 && d <= (long long)max_gap + 1 && c_since[t] <= o_last[e];
+            }
+            s_new[t] = ext ? 0 : 1;
+            s_app[t] = e < 0 ? 1 : 0;
+        }
+        __syncthreads();
+        int n_new = 0, n_app = 0, my_new = 0, my_app = 0;   // new relations take ids in ranked order
+        for (int q = 0; q < n; ++q) {
+            if (q == t) my_new = n_new, my_app = n_app;
+            n_new += s_new[q];
+            n_app += s_app[q];
+        }
+        int id = 0, cnt = 1;
+        double sum = 0.0;
+        if (t < n) {
+            sum = c_score[t];
+            if (ext) {
+                id = o_id[e];
+                cnt = o_cnt[e] + 1;
+                sum = o_sum[e] + c_score[t];
+            } else {
+                id = next + my_new;
+            }
+            if (e >= 0) {                                // keys of a frame are distinct: the entry is this thread's alone
+                o_id[e] = id;
+                o_cnt[e] = cnt;
+                o_sum[e] = sum;
+                o_last[e] = fno;
+            }
+            if ((long long)base + id < n_preds) {        // id < predictions seen so far in this video
+                if (!ext) rel_start[base + id] = fno;
+                rel_end[base + id] = fno + 1;
+                rel_len[base + id] = cnt;
+                rel_score[base + id] = sum / (double)cnt;
+            }
+            rel_id[p0 + c_src[t]] = id;
+        }
+        next += n_new;
+        __syncthreads();                                 // the table is updated in place
+        // 4. drop what no later frame can reach (the next frame number is at least fno + 1), keeping the order
+        int kept = 0;
+        int q_key[VT_PER][3], q_last[VT_PER], q_cnt[VT_PER], q_id[VT_PER];
+        double q_sum[VT_PER];
+        unsigned keep = 0;                               // bit i: entry t * VT_PER + i stays
+        if (!bad) {
+#pragma unroll
+            for (int i = 0; i < VT_PER; ++i) {
+                const int s = t * VT_PER + i;
+                if (s < m && (long long)o_last[s] >= (long long)fno - max_gap) {
+                    q_key[i][0] = o_key[0][s], q_key[i][1] = o_key[1][s], q_key[i][2] = o_key[2][s];
+                    q_last[i] = o_last[s], q_cnt[i] = o_cnt[s], q_id[i] = o_id[s];
+                    q_sum[i] = o_sum[s];
+                    keep |= 1u << i;
+                    ++kept;
+                }
+            }
+        }
+        int incl = kept;
+        for (int o = 1; o < 64; o <<= 1) {
+            const int y = __shfl_up(incl, o);
+            if ((t & 63) >= o) incl += y;
+        }
+        if ((t & 63) == 63) s_wsum[t >> 6] = incl;
+        __syncthreads();                                 // every kept entry is in a register: the table may be overwritten
+        if (!bad) {
+            int dst = incl - kept, total = 0;
+            for (int w = 0; w < VA_THREADS / 64; ++w) {
+                if (w < (t >> 6)) dst += s_wsum[w];
+                total += s_wsum[w];
+            }
+#pragma unroll
+            for (int i = 0; i < VT_PER; ++i) {
+                if (!((keep >> i) & 1u)) continue;
+                const int s = dst++;                     // dst <= t * VT_PER + i: never past what was read
+                o_key[0][s] = q_key[i][0], o_key[1][s] = q_key[i][1], o_key[2][s] = q_key[i][2];
+                o_last[s] = q_last[i], o_cnt[s] = q_cnt[i], o_id[s] = q_id[i];
+                o_sum[s] = q_sum[i];
+            }
+            if (t < n && e < 0) {                        // 5. the relations whose key had no entry
+                const int s = total + my_app;
+                if (s < VT_CAP) {
+                    o_key[0][s] = c_key[t][0], o_key[1][s] = c_key[t][1], o_key[2][s] = c_key[t][2];
+                    o_last[s] = fno, o_cnt[s] = 1, o_id[s] = id;
+                    o_sum[s] = sum;
+                } else {
+                    atomicMax(status, f + 1);            // past the bound that ascending frame numbers give: not reached
+                }
+            }
+            m = total + n_app < VT_CAP ? total + n_app : VT_CAP;
+            prev_no = fno;
+            any = true;
+        }
+        __syncthreads();                                 // the table is compacted; the frame's arrays are free
+    }
+    if (t == 0) n_rel[v] = next;
+}
+
+extern "C" size_t i2v_video_associate_tracks_workspace_bytes(int32_t n_videos, int32_t n_frames, int32_t n_preds) {
+    (void)n_videos; (void)n_frames; (void)n_preds;
+    return I2V_STATUS_BYTES;                             // the status word
+}
+
+extern "C" int32_t i2v_video_associate_tracks(const int32_t* frame_off, const int32_t* frame_no, const int32_t* pred_off,
+                                              const double* score, const int32_t* key, const int32_t* since,
+                                              int32_t n_videos, int32_t n_frames, int32_t n_preds, int32_t max_gap,
+                                              int32_t* rel_id, int32_t* rel_start, int32_t* rel_end, int32_t* rel_len,
+                                              double* rel_score, int32_t* n_rel, void* ws, size_t ws_bytes, void* stream) {
+    I2V_CHECK_ARG(n_videos >= 0 && n_frames >= 0 && n_preds >= 0, "video_associate_tracks: negative count");
+    I2V_CHECK_ARG(max_gap >= 0 && max_gap <= VT_MAXGAP, "video_associate_tracks: max_gap lies in [0, %d] (got %d)", VT_MAXGAP,
+                  max_gap);
+    I2V_CHECK_ARG(frame_off && pred_off && (n_frames == 0 || frame_no) && (n_videos == 0 || n_rel),
+                  "video_associate_tracks: null pointer");
+    I2V_CHECK_ARG(n_preds == 0 || (score && key && since && rel_id && rel_start && rel_end && rel_len && rel_score),
+                  "video_associate_tracks: null pointer");
+    I2V_CHECK_ARG(ws && ws_bytes >= i2v_video_associate_tracks_workspace_bytes(n_videos, n_frames, n_preds),
+                  "video_associate_tracks: workspace too small");
+    if (n_videos == 0) return I2V_OK;
+    hipStream_t st = (hipStream_t)stream;
+    I2V_CLEAR_STATUS(ws, 0, 4, st, "video_associate_tracks: clearing the status word failed");
+    video_associate_tracks_kernel<<<n_videos, VA_THREADS, 0, st>>>(frame_off, frame_no, pred_off, score, key, since, n_frames,
+                                                                   n_preds, max_gap, rel_id, rel_start, rel_end, rel_len, rel_score,
+                                                                   n_rel, (int*)ws);
+    I2V_CHECK_LAUNCH("video_associate_tracks");
+    return I2V_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
 // Trajectory overlap (viou) and the greedy matching of eval_detection_scores
 // ---------------------------------------------------------------------------------------------------------------------
 

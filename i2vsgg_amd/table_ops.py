@@ -100,6 +100,34 @@ def video_associate(frame_off, frame_no, pred_off, score, triplet, boxes, device
     return rel_id, rel_start, rel_len, rel_score, n_rel
 
 
+def video_associate_tracks(frame_off, frame_no, pred_off, score, key, since, max_gap=0, device=None, read_status=True):
+    """Association along object tracks for a packed batch of videos in one launch (include/i2vsgg_hip.h,
+    i2v_video_associate_tracks; ``video.pack_track_frames`` builds the arrays, ``video.associate_tracks_arrays_host`` is the
+    numpy form).  Arrays or tensors: frame_off (V+1), frame_no (F), pred_off (F+1) int32, score (P) fp64, key (P,3) int32,
+    since (P) int32; ``max_gap`` an int in [0, 7].  Returns device tensors (rel_id (P), rel_start (P), rel_end (P), rel_len (P)
+    int32, rel_score (P) fp64, n_rel (V) int32).  ``read_status=False`` returns what the kernel wrote for the well-formed
+    frames without raising for the malformed ones."""
+    dev = _device(device, "video.associate_tracks(device=None)")
+    if isinstance(max_gap, bool) or int(max_gap) != max_gap:
+        raise ValueError("video_associate_tracks: max_gap is an int in [0, 7] (got %r)" % (max_gap,))
+    frame_off, frame_no, pred_off, key, since = _stage(dev, torch.int32, frame_off, frame_no, pred_off, key, since)
+    score, = _stage(dev, torch.float64, score)
+    V, F, P = frame_off.numel() - 1, frame_no.numel(), score.numel()
+    if V < 0 or pred_off.numel() != F + 1 or key.numel() != 3 * P or since.numel() != P:
+        raise ValueError("video_associate_tracks: array sizes do not agree")
+    rel_id, rel_start, rel_end, rel_len = (torch.zeros((P,), device=dev, dtype=torch.int32) for _ in range(4))
+    rel_score = torch.zeros((P,), device=dev, dtype=torch.float64)
+    n_rel = torch.zeros((V,), device=dev, dtype=torch.int32)
+    ws = _launch(dev, "video_associate_tracks", lambda *tail: lib.i2v_video_associate_tracks(
+        ptr(frame_off), ptr(frame_no), ptr(pred_off), ptr(score), ptr(key), ptr(since), V, F, P, int(max_gap), ptr(rel_id),
+        ptr(rel_start), ptr(rel_end), ptr(rel_len), ptr(rel_score), ptr(n_rel), *tail),
+        lib.i2v_video_associate_tracks_workspace_bytes(V, F, P), "video")
+    if read_status and V > 0:
+        _status(ws, 0, "video_associate_tracks", "frame", "the tables are out of range, or a frame holds more than 100 predictions, "
+                "a frame number that does not ascend or a repeated key, at")
+    return rel_id, rel_start, rel_end, rel_len, rel_score, n_rel
+
+
 def video_viou_match(pred_off, pred_rel, pred_score, gt_off, gt_rel, boxes, viou_threshold=0.5, device=None):
     """Trajectory overlaps and the detection metric's greedy matching for a packed batch of videos
     (include/i2vsgg_hip.h, i2v_video_viou_match; ``video.pack_eval`` builds the arrays).  Returns device tensors (ov

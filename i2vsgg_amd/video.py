@@ -10,6 +10,11 @@ association and the trajectory overlaps / matching of the detection metric are H
 ``device`` is given.  With ``device=None`` the same rules run as plain numpy on the host: evaluation scripts work on a
 machine without a GPU, and the kernels have something to be compared with.  Both paths share the packing, the selection
 and the gather, and both do their arithmetic in float64 in the same operation order, so they agree bit for bit.
+
+``associate_tracks`` is a second association mode for boxes that carry track ids (Seq-NMS's): relations are keyed by the tracks
+of their subject and object instead of by box overlap and may bridge up to ``max_gap`` frames.  Its rules are this project's
+own and stand in its docstring; it has its own packer, host form, kernel and gather and shares nothing with ``associate`` but
+the constants.
 """
 import numpy as np
 
@@ -60,11 +65,13 @@ def fill_empty_frames(frames):
     return out
 
 
-def from_frame_results(results, frame_to_video=None):
+def from_frame_results(results, frame_to_video=None, tracks=None):
     """What ``test_sgg_emb.py`` pickles -- {frame path: (rlp_labels, tuple_confs, sub_bboxes, obj_bboxes, rel_idex)}, five
     Nones for a frame without pairs -- as ``frame_relations`` {vid: [[fno, [[conf, [s, p, o], [sub_box, obj_box],
     rel_idex], ...]], ...]}.  ``frame_to_video`` maps a path to (vid, fno): a dict or a callable; None: one video "0",
-    frames numbered in the order of ``results``."""
+    frames numbered in the order of ``results``.  ``tracks``: the per-frame box pickle the loop ran on (keyed by frame path or
+    file name, ``tids`` one int per box); every prediction then gets a fifth element [sub_tid, obj_tid], and what
+    ``associate_tracks`` refuses is refused here."""
     out = {}
     for k, (path, res) in enumerate(results.items()):
         if frame_to_video is None:
@@ -79,6 +86,12 @@ def from_frame_results(results, frame_to_video=None):
             labels, sub, obj = np.asarray(labels).tolist(), np.asarray(sub).tolist(), np.asarray(obj).tolist()
             confs, idx = confs.tolist(), np.asarray(idx).tolist()
             preds = [[confs[j], labels[j], [sub[j], obj[j]], idx[j]] for j in range(len(confs))]
+        if tracks is not None:
+            where = "video %r frame %d" % (vid, int(fno))
+            boxes, classes, tids = _frame_tracks(_key_of(tracks, path), where)
+            _, _, _, bi, bj = _resolve(preds, boxes, classes, where)
+            for j, p in enumerate(preds):
+                p.append([int(tids[bi[j]]), int(tids[bj[j]])])
         out.setdefault(vid, []).append([fno, preds])
     return out
 
@@ -269,6 +282,308 @@ def associate(frame_relations, device=None, names=None, stats=None):
         res = [t.cpu().numpy() for t in ops.video_associate(pk.frame_off, pk.frame_no, pk.pred_off, pk.score, pk.triplet,
                                                             pk.boxes, device=device)]
     return gather_relations(pk, *res, names=names)
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# association along object tracks
+# ------------------------------------------------------------------------------------------------------------------
+MAX_GAP = 7                  # frames a relation may stay out of its frames' lists and still go on
+
+
+def _key_of(tracks, path):
+    """The annotation of a frame: by the key as given, then by its file name (the pickle's own key)."""
+    if path in tracks:
+        return tracks[path]
+    name = path.split("/")[-1] if isinstance(path, str) else path
+    return tracks.get(name)
+
+
+def tracks_by_frame(tracks, paths, frame_to_video=None):
+    """The per-frame box pickle {frame key: annotation} as {(vid, fno): annotation} for the frames ``paths``, numbered as
+    ``from_frame_results`` numbers them.  A frame without an entry is left out (the packer names it)."""
+    out = {}
+    for k, path in enumerate(paths):
+        if frame_to_video is None:
+            vid, fno = "0", k
+        elif callable(frame_to_video):
+            vid, fno = frame_to_video(path)
+        else:
+            vid, fno = frame_to_video[path]
+        anno = _key_of(tracks, path)
+        if anno is not None:
+            out[(vid, int(fno))] = anno
+    return out
+
+
+def _frame_tracks(anno, where):
+    """One frame of the box pickle as (boxes (n,4) float64, classes (n,) int64, tids (n,) int64), or ``ValueError``."""
+    if anno is None:
+        raise ValueError("video tracks: %s has no entry in the box pickle" % where)
+    boxes = np.asarray(anno["boxes"], np.float64).reshape(-1, 4)
+    classes = np.asarray(anno["box_classes"], np.int64).reshape(-1)
+    n = len(boxes)
+    tids = anno.get("tids")
+    if tids is None:
+        raise ValueError("video tracks: %s has no tids: the pickle is not a tracked one (seqnms.to_annotations)" % where)
+    flat = list(tids)
+    if len(flat) != n or len(classes) != n or not all(isinstance(t, (int, np.integer)) and not isinstance(t, bool) for t in flat):
+        raise ValueError("video tracks: %s: tids holds one int per box (%d boxes); [subject_tid, object_tid] per relation is the "
+                         "recognition set's layout, not this one" % (where, n))
+    tids = np.asarray(flat, np.int64).reshape(-1)
+    if (tids < 0).any():
+        raise ValueError("video tracks: %s has a negative tid" % where)
+    if len(set(zip(classes.tolist(), tids.tolist()))) != n:
+        raise ValueError("video tracks: %s has two boxes with the same (class, tid)" % where)
+    return boxes, classes, tids
+
+
+def _resolve(preds, boxes, classes, where):
+    """The subject and object box index of a frame's predictions from their ``rel_idex`` (ordered pairs, i-major over i != j),
+    checked against the prediction's own boxes and classes.  -> (score (k,), triplet (k,3) int64, idex (k,), i (k,), j (k,))."""
+    n, k = len(boxes), len(preds)
+    score = np.asarray([p[0] for p in preds], np.float64).reshape(k)
+    trip = np.asarray([p[1] for p in preds], np.float64).reshape(k, 3).astype(np.int64)
+    pbox = np.asarray([list(p[2][0]) + list(p[2][1]) for p in preds], np.float64).reshape(k, 8)
+    idex = np.asarray([p[3] for p in preds], np.int64).reshape(k)
+    if k == 0:
+        return score, trip, idex, idex, idex
+    if n < 2 or (idex < 0).any() or (idex >= n * (n - 1)).any():
+        raise ValueError("video tracks: %s: a rel_idex lies outside the %d ordered pairs of %d boxes" % (where, n * max(n - 1, 0), n))
+    i, j = idex // (n - 1), idex % (n - 1)
+    j = j + (j >= i)
+    if (pbox[:, :4].view(np.int64) != boxes[i].view(np.int64)).any() or (pbox[:, 4:].view(np.int64) != boxes[j].view(np.int64)).any():
+        raise ValueError("video tracks: %s: a prediction's box is not the pickle's box its rel_idex names: the wrong pickle?" % where)
+    if (trip[:, 0] != classes[i]).any() or (trip[:, 2] != classes[j]).any():
+        raise ValueError("video tracks: %s: a triplet's classes disagree with the pickle's box classes" % where)
+    return score, trip, idex, i, j
+
+
+class PackedTracks(object):
+    """Flat arrays of a batch of videos (the layout of ``ops.video_associate_tracks``) and, for the gather, per video the
+    objects [(class, tid), ...] by object index and per frame number (object index (n,), boxes (n,4))."""
+
+    def __init__(self, vids, frame_off, frame_no, pred_off, score, key, since, rel_idex, objects, frames):
+        self.vids, self.frame_off, self.frame_no, self.pred_off = vids, frame_off, frame_no, pred_off
+        self.score, self.key, self.since, self.rel_idex, self.objects, self.frames = score, key, since, rel_idex, objects, frames
+
+
+def _check_gap(max_gap):
+    if isinstance(max_gap, bool) or not isinstance(max_gap, (int, np.integer)) or not 0 <= max_gap <= MAX_GAP:
+        raise ValueError("video tracks: max_gap is an int in [0, %d] (got %r)" % (MAX_GAP, max_gap))
+    return int(max_gap)
+
+
+def pack_track_frames(frame_relations, tracks, frame_to_video=None):
+    """The tables of the track mode (``associate_tracks`` states the rules).  ``tracks``: {(vid, fno): annotation}; with
+    ``frame_to_video`` (a dict path -> (vid, fno)) the box pickle as it is, keyed by frame path or file name.  Every video of
+    ``frame_relations`` takes part, in its order, also one without frames or predictions."""
+    if frame_to_video is not None:
+        tracks = tracks_by_frame(tracks, list(frame_to_video), frame_to_video)
+    vids, frame_off, frame_no, counts = [], [0], [], []
+    score, key, since, idex, objects, tables = [], [], [], [], [], []
+    for vid, frames in frame_relations.items():
+        frames = sorted(frames, key=lambda fr: int(fr[0]))
+        vids.append(vid)
+        index, run, objs, table = {}, {}, [], {}         # (class, tid) -> object index; object index -> [last frame, run start]
+        for fno, preds in frames:
+            fno = int(fno)
+            where = "video %r frame %d" % (vid, fno)
+            if fno in table:
+                raise ValueError("video tracks: %s appears twice" % where)
+            boxes, classes, tids = _frame_tracks(tracks.get((vid, fno)), where)
+            oid = np.empty(len(boxes), np.int64)
+            start = np.empty(len(boxes), np.int64)
+            for b, ct in enumerate(zip(classes.tolist(), tids.tolist())):
+                o = index.setdefault(ct, len(objs))
+                if o == len(objs):
+                    objs.append(ct)
+                r = run.get(o)
+                run[o] = r = [fno, r[1] if r is not None and r[0] == fno - 1 else fno]
+                oid[b], start[b] = o, r[1]
+            table[fno] = (oid, boxes)
+            s, trip, ix, i, j = _resolve(preds, boxes, classes, where)
+            for p, pred in enumerate(preds):
+                if len(pred) > 4 and [int(x) for x in pred[4]] != [int(tids[i[p]]), int(tids[j[p]])]:
+                    raise ValueError("video tracks: %s: a prediction's tids are not those of the boxes its rel_idex names" % where)
+            order = np.argsort(-s, kind="stable")[:MAX_PER_FRAME]
+            frame_no.append(fno)
+            counts.append(len(order))
+            if len(order):
+                score.append(s[order])
+                key.append(np.stack([oid[i[order]], trip[order, 1], oid[j[order]]], 1))
+                since.append(np.maximum(start[i[order]], start[j[order]]))
+                idex.append(ix[order])
+        frame_off.append(len(frame_no))
+        objects.append(objs)
+        tables.append(table)
+    pred_off = offsets(counts, "video.pack_track_frames: more than 2^31 predictions")
+    return PackedTracks(vids, np.asarray(frame_off, np.int32), np.asarray(frame_no, np.int32), pred_off, cat(score, (), np.float64),
+                        cat(key, (3,), np.int64).astype(np.int32), cat(since, (), np.int64).astype(np.int32),
+                        cat(idex, (), np.int64), objects, tables)
+
+
+def associate_tracks_arrays_host(pk, max_gap=0):
+    """The rules of ``ops.video_associate_tracks`` in numpy, on the same arrays, with the same outputs (rel_id, rel_start,
+    rel_end, rel_len, rel_score, n_rel); one pass of array operations per frame.  A table the kernel would report (a frame of
+    more than 100 predictions, a frame number that does not ascend, a repeated key) raises ``ValueError``."""
+    G = _check_gap(max_gap)
+    P, V = len(pk.score), len(pk.frame_off) - 1
+    rel_id = np.zeros(P, np.int32)
+    rel_start, rel_end, rel_len = np.zeros(P, np.int32), np.zeros(P, np.int32), np.zeros(P, np.int32)
+    rel_score, n_rel = np.zeros(P, np.float64), np.zeros(V, np.int32)
+    key = np.asarray(pk.key, np.int64).reshape(-1, 3)
+    for v in range(V):
+        f0, f1 = int(pk.frame_off[v]), int(pk.frame_off[v + 1])
+        if f1 == f0:
+            continue
+        base, end = int(pk.pred_off[f0]), int(pk.pred_off[f1])
+        _, kid = np.unique(key[base:end], axis=0, return_inverse=True)       # the video's keys, densely numbered
+        kid = kid.reshape(-1)
+        n_keys = int(kid.max()) + 1 if len(kid) else 0
+        o_id, o_last = np.full(n_keys, -1, np.int64), np.zeros(n_keys, np.int64)   # the open relation of every key
+        r_start, r_end, r_len = np.zeros(end - base, np.int32), np.zeros(end - base, np.int32), np.zeros(end - base, np.int32)
+        r_sum = np.zeros(end - base, np.float64)
+        nxt, prev_no = 0, None
+        for f in range(f0, f1):
+            p0, p1 = int(pk.pred_off[f]), int(pk.pred_off[f + 1])
+            fno = int(pk.frame_no[f])
+            if p1 - p0 > MAX_PER_FRAME or (prev_no is not None and fno <= prev_no):
+                raise ValueError("video tracks: frame %d of the table holds more than %d predictions or a frame number that "
+                                 "does not ascend" % (f, MAX_PER_FRAME))
+            prev_no = fno
+            if p1 == p0:
+                continue
+            order = np.argsort(-pk.score[p0:p1], kind="stable")
+            S, K, since = pk.score[p0:p1][order], kid[p0 - base:p1 - base][order], pk.since[p0:p1][order].astype(np.int64)
+            if len(np.unique(K)) != len(K):
+                raise ValueError("video tracks: frame %d of the table repeats a key" % f)
+            L = o_last[K]
+            ext = (o_id[K] >= 0) & (fno - L >= 1) & (fno - L <= G + 1) & (since <= L)
+            new = ~ext
+            ids = np.where(ext, o_id[K], nxt + np.cumsum(new) - 1)
+            nxt += int(new.sum())
+            r_start[ids[new]] = fno
+            r_end[ids] = fno + 1
+            r_sum[ids] = np.where(new, S, r_sum[ids] + S)        # ids of one frame are distinct
+            r_len[ids] = np.where(new, 1, r_len[ids] + 1)
+            o_id[K], o_last[K] = ids, fno
+            rel_id[p0 + order] = ids
+        n_rel[v] = nxt
+        rel_start[base:base + nxt], rel_end[base:base + nxt], rel_len[base:base + nxt] = r_start[:nxt], r_end[:nxt], r_len[:nxt]
+        rel_score[base:base + nxt] = r_sum[:nxt] / np.maximum(r_len[:nxt], 1)
+    return rel_id, rel_start, rel_end, rel_len, rel_score, n_rel
+
+
+def gather_track_relations(pk, rel_id, rel_start, rel_end, rel_len, rel_score, n_rel, names=None):
+    """Per video: drop relations of fewer than 10 members, order the rest by score (descending, stable in creation order),
+    keep 200, and read each one's trajectories and pair indices from its two tracks' boxes, for every frame of the duration."""
+    out = {}
+    for v, vid in enumerate(pk.vids):
+        f0, f1 = int(pk.frame_off[v]), int(pk.frame_off[v + 1])
+        base, end = int(pk.pred_off[f0]), int(pk.pred_off[f1])
+        nr = int(n_rel[v])
+        keep = np.nonzero(rel_len[base:base + nr] >= MIN_MEMBERS)[0]
+        keep = keep[np.argsort(-rel_score[base + keep], kind="stable")][:MAX_PER_VIDEO]
+        ids = rel_id[base:end]
+        by_rel = np.argsort(ids, kind="stable")                  # members of a relation, in frame order
+        first = np.searchsorted(ids[by_rel], np.arange(nr + 1))
+        member_frame = np.repeat(pk.frame_no[f0:f1], np.diff(pk.pred_off[f0:f1 + 1]))
+        objs, table = pk.objects[v], pk.frames[v]
+        rels = []
+        for k in keep:
+            mem = by_rel[first[k]:first[k + 1]]
+            so, p, oo = (int(x) for x in pk.key[base + mem[0]])
+            start, stop = int(rel_start[base + k]), int(rel_end[base + k])
+            own = dict(zip(member_frame[mem].tolist(), pk.rel_idex[base + mem].tolist()))
+            sub, obj, idex = [], [], []
+            for fno in range(start, stop):
+                oid, boxes = table[fno]                          # ``since``: both tracks have a box in every frame of the duration
+                i, j = int(np.nonzero(oid == so)[0][0]), int(np.nonzero(oid == oo)[0][0])
+                pair = i * (len(oid) - 1) + j - (j > i)
+                assert own.get(fno, pair) == pair, (vid, fno, own[fno], pair)
+                sub.append(boxes[i].tolist())
+                obj.append(boxes[j].tolist())
+                idex.append(pair)
+            s, o = objs[so][0], objs[oo][0]
+            rels.append({
+                "triplet": [names[0][s], names[1][p], names[0][o]] if names is not None else [s, p, o],
+                "score": float(rel_score[base + k]),
+                "duration": [start, stop],
+                "sub_traj": sub,
+                "obj_traj": obj,
+                "rel_idex": idex,
+                "sub_tid": int(objs[so][1]),
+                "obj_tid": int(objs[oo][1]),
+                "members": int(rel_len[base + k]),
+            })
+        out[vid] = rels
+    return out
+
+
+def gap_frames(relations):
+    """Frames of the relations' durations that are not members: what ``max_gap`` bridged."""
+    return sum(r["duration"][1] - r["duration"][0] - r["members"] for rels in relations.values() for r in rels)
+
+
+def associate_tracks(frame_relations, tracks, max_gap=0, device=None, names=None, frame_to_video=None):
+    """Association along the object tracks that Seq-NMS computed: a second mode beside ``associate`` for boxes that carry a
+    track id.  ``associate`` rediscovers identity frame by frame from box overlaps; here identity is given, so two objects of
+    one class that pass each other keep their relations, and a relation that leaves its frames' top 100 for a few frames
+    goes on.  The rules are this project's own (the reference has no tracks); both forms follow them.
+
+    Inputs.  ``frame_relations`` as ``from_frame_results`` returns it, and ``tracks``, the per-frame box pickle the frame loop
+    ran on, in the layout of ``seqnms.to_annotations``: per frame ``boxes``, ``box_classes`` and ``tids`` with one int per box,
+    track ids per (video, class).  ``tracks`` is keyed by (vid, fno); with ``frame_to_video`` (a dict path -> (vid, fno)) it is
+    the pickle as it is.
+
+    Identity.  A track is (video, class, tid).  Per video, tracks get a dense object index in order of first appearance
+    (frames ascending, box order within a frame).  A prediction's ``rel_idex`` is its ordered-pair index (i-major over i != j):
+    for n boxes i = p // (n-1), j' = p % (n-1), j = j' + (j' >= i) are its subject and object box, and so its two tracks.
+
+    Refused (``ValueError`` naming the frame): a result frame missing from the pickle; no ``tids``, or ``tids`` not of one int
+    per box (``synthetic.recognition_set`` uses the key for [subject_tid, object_tid] per relation); a negative tid; two
+    boxes of one frame with the same (class, tid); a prediction whose subject or object box is not bit-equal to the pickle's
+    box it resolves to (the wrong pickle); classes that disagree with the triplet; a frame number twice in a video.
+
+    Per frame the predictions are ordered by descending score, stable, and cut to 100.  ``fill_empty_frames`` is not applied:
+    the gap rule serves an empty frame.
+
+    Key: (subject object index, predicate, object object index); distinct within a frame by what is refused.
+
+    Presence.  Every prediction has ``since``, the larger of its two tracks' run starts: the first frame number of the maximal
+    run of consecutive frame numbers of the video, ending at this frame, in which the track has a box in the pickle.  Top-100
+    membership plays no part in it.
+
+    Extension.  A video has at most one open relation per key.  The prediction at frame number f extends the open relation of
+    its key, whose last member is at frame number L, iff 1 <= f - L <= max_gap + 1 and since <= L; otherwise it opens a
+    relation, which takes the place of the open one of its key (that one can never be extended again: a later ``since`` is no
+    smaller).  ``max_gap`` is an int in [0, 7]; with 0 a relation must appear in consecutive frames, as in the box mode, and the
+    ``since`` condition cannot fail.  A missing frame number, or a frame where either track has no box, ends the relation
+    whatever ``max_gap`` is: ``since`` then lies past L.
+
+    Numbering: new relations get ids 0, 1, 2, ... per video, frames ascending, within a frame in ranked order.
+
+    Score: the float64 sum of the members' scores in member order, from the first member's score, divided by the number of
+    members.  Gap frames are not members: they enter neither the mean nor the 10-member rule.
+
+    Selection as in ``gather_relations``: at least 10 members, descending score stable in creation order, the first 200.
+
+    Output per relation: ``triplet``, ``score``, ``duration`` = [first member's frame, last member's frame + 1), ``sub_traj`` /
+    ``obj_traj`` (the tracks' boxes from the pickle for EVERY frame of the duration), ``rel_idex`` (per frame of the duration the
+    pair index of (subject box, object box) in that frame; on member frames it equals the prediction's own, which is
+    asserted), ``sub_tid``, ``obj_tid`` and ``members``.  ``relation_features.pack`` / ``pool`` and ``pack_eval`` / ``evaluate``
+    read it unchanged.
+
+    ``device``: all videos in one kernel launch on that GPU (``ops.video_associate_tracks``); None: the host form."""
+    max_gap = _check_gap(max_gap)
+    pk = pack_track_frames(frame_relations, tracks, frame_to_video)
+    if device is None:
+        res = associate_tracks_arrays_host(pk, max_gap)
+    else:
+        from . import ops
+        res = [t.cpu().numpy() for t in ops.video_associate_tracks(pk.frame_off, pk.frame_no, pk.pred_off, pk.score, pk.key, pk.since,
+                                                                   max_gap, device=device)]
+    return gather_track_relations(pk, *res, names=names)
 
 
 # ------------------------------------------------------------------------------------------------------------------

@@ -232,6 +232,27 @@ int32_t i2v_video_associate(const int32_t* frame_off, const int32_t* frame_no, c
                             int32_t n_videos, int32_t n_frames, int32_t n_preds, int32_t max_per_frame,
                             int32_t* rel_id, int32_t* rel_start, int32_t* rel_len, double* rel_score,
                             int32_t* n_rel, void* workspace, size_t workspace_bytes, void* stream);
+/* Association along object tracks: this project's own mode for boxes that carry track ids (the rules are stated in full
+ * in i2vsgg_amd/video.py, associate_tracks; video.pack_track_frames builds the tables).  frame_off / frame_no / pred_off
+ * as above, frame numbers strictly ascending within a video, at most 100 predictions per frame; per prediction score
+ * (fp64), key (3 x int32: subject object index, predicate, object object index; distinct within a frame) and since
+ * (int32: the first frame number from which both objects have a box in every frame up to this one).  No boxes reach
+ * the device.  A frame's predictions are taken in descending score, equal scores in the given order.  A video has at
+ * most one open relation per key.  The prediction at frame number f extends the open relation of its key, whose last
+ * member is at frame number L, iff 1 <= f - L <= max_gap + 1 and since <= L; otherwise it opens a relation, which
+ * replaces the open one of its key.  max_gap lies in [0, 7] (checked before the launch, without a device).  Outputs:
+ * rel_id (n_preds), and per relation, at index pred_off[frame_off[v]] + k as above, rel_start (first member's frame
+ * number), rel_end (last member's frame number + 1), rel_len (members; gap frames are not members) and rel_score (the
+ * members' scores added in member order from the first, divided by rel_len: fp64, one sequence of adds, no atomics);
+ * n_rel (n_videos).  Entries past a video's n_rel are not written.  Status word: 0, or 1 + the index of a frame that was
+ * skipped as if empty (table entries out of range, more than 100 predictions, a frame number that does not ascend, a
+ * repeated key), or 1 + n_frames for a video whose frame range lies outside the table (its n_rel is 0). */
+size_t  i2v_video_associate_tracks_workspace_bytes(int32_t n_videos, int32_t n_frames, int32_t n_preds);
+int32_t i2v_video_associate_tracks(const int32_t* frame_off, const int32_t* frame_no, const int32_t* pred_off,
+                                   const double* score, const int32_t* key, const int32_t* since,
+                                   int32_t n_videos, int32_t n_frames, int32_t n_preds, int32_t max_gap,
+                                   int32_t* rel_id, int32_t* rel_start, int32_t* rel_end, int32_t* rel_len,
+                                   double* rel_score, int32_t* n_rel, void* workspace, size_t workspace_bytes, void* stream);
 /* replaces viou (:221-262) and the greedy loop of eval_detection_scores (:265-288).  A relation is a row of 10 int32:
  * video, s_cid, pid, o_cid, fstart, fend, sub_off, sub_len, obj_off, obj_len; the trajectories are runs of `boxes`
  * (n_boxes x 4 fp64).  Video v owns predictions [pred_off[v], pred_off[v+1]) (at most max_pred <= 200) and ground truths

@@ -2,7 +2,9 @@
 """Relation test loop up to the video level (test_net_SGG_emb.py:196-211 and :308-313): the per-frame part is
 ``test_sgg_emb.py``'s, unchanged (same flags, same ``relations.pkl``); its top-100 triplets per frame are then linked into video
 relation instances on the GPU (``i2vsgg_amd.video.associate``) and written to ``video_relations.json`` beside ``relations.pkl``,
-the file ``eval_video_relations.py`` scores.  ``--relations FILE`` skips the frame loop and starts from a pickle that an earlier
+the file ``eval_video_relations.py`` scores.  ``--associate tracks`` links along the track ids of the boxes the loop ran on
+instead (``i2vsgg_amd.video.associate_tracks``; ``--max_gap G`` lets a relation miss up to G frames, ``--tracks FILE`` names the box
+pickle, by default the loop's ``--target_gt_rels_path``).  ``--relations FILE`` skips the frame loop and starts from a pickle that an earlier
 run wrote.  The synthetic imdb has no video ids: ``--frames_per_video N`` takes the frames in the order of their paths (the
 loader's order depends on the frames' aspect ratios) and makes every N consecutive ones a video, numbered from 0 (default: the
 whole imdb is one video, frame number = index).  ``--save_videofeat_path DIR`` adds the hand-off to the video-level stage
@@ -24,6 +26,10 @@ sys.path.insert(0, ROOT)
 os.environ.setdefault("DEBUG_CLR_GRAPH_PACKET_CAPTURE", "0")     # before HIP initialises: i2vsgg_amd/__init__.py
 
 
+NO_TRACKS = ("--associate tracks reads the track ids of the boxes the frame loop ran on: pass that pickle (tracked_boxes.pkl of "
+             "track_detections.py) as --tracks, or as --target_gt_rels_path when the frame loop runs")
+
+
 def main(argv=None, hold=None):
     p = argparse.ArgumentParser(description="Relation test loop + frame-to-video association on MI355X", add_help=False)
     p.add_argument("--frames_per_video", type=int, default=0)
@@ -36,7 +42,17 @@ def main(argv=None, hold=None):
     p.add_argument("--save_videofeat_path", default="", help="write DIR/<predicate>/<vid>_<pno>.npy, one pooled relation "
                    "feature per video relation (lib/utils.py:100-132); the frame features stay on the device in between")
     p.add_argument("--feat_arena_mb", type=float, default=4096, help="largest device store of relation features, MiB")
+    p.add_argument("--associate", choices=["boxes", "tracks"], default="boxes", help="boxes: the reference's association by box "
+                   "overlap; tracks: along the track ids of the boxes the frame loop ran on (video.associate_tracks)")
+    p.add_argument("--max_gap", type=int, default=0, help="with --associate tracks: frames (0..7) a relation may stay out of its "
+                   "frames' top 100 and still go on")
+    p.add_argument("--tracks", default="", help="with --associate tracks: the per-frame box pickle with tids (default: the frame "
+                   "loop's --target_gt_rels_path; required with --relations)")
     a, rest = p.parse_known_args(argv)
+    if a.associate != "tracks" and (a.max_gap != 0 or a.tracks):
+        raise SystemExit("--max_gap and --tracks belong to --associate tracks: give it")
+    if a.associate == "tracks" and not 0 <= a.max_gap <= 7:
+        raise SystemExit("--max_gap lies in 0..7 (got %d)" % a.max_gap)
     import test_sgg_emb as frames
     from i2vsgg_amd import video
     keep = bool(a.save_feat_path or a.save_videofeat_path)
@@ -47,11 +63,16 @@ def main(argv=None, hold=None):
         if keep:
             raise SystemExit("--save_feat_path / --save_videofeat_path need the frame loop (the features live on the device during "
                              "the run); from files of an earlier run use pool_relation_features.py")
+        if a.associate == "tracks" and not a.tracks:
+            raise SystemExit(NO_TRACKS)
         with open(a.relations, "rb") as f:
             results = pickle.load(f)
         out_dir = os.path.dirname(os.path.abspath(a.relations))
     else:
         b = frames.parse_args(rest)
+        a.tracks = a.tracks or b.target_gt_rels_path
+        if a.associate == "tracks" and not a.tracks:     # before the frame loop runs for nothing
+            raise SystemExit(NO_TRACKS)
         if keep:                                         # the loop's code is unchanged: the block makes its steps keep pre_feat
             from i2vsgg_amd import eval as ev, relation_features as rf
             with ev.keeping_relation_features(rf.ArenaSink("cuda:0", a.feat_arena_mb)) as sink:
@@ -74,12 +95,20 @@ def main(argv=None, hold=None):
         n = rf.save_frame_feats(sink.arena, a.save_feat_path) if a.save_frame_feats else 0
         print("wrote %s/semantic_embedding.npy and the features of %d frames" % (a.save_feat_path, n))
     t0 = time.time()
-    relations = video.associate(video.from_frame_results(results, index), device=None if a.cpu else "cuda:0")
+    mode = ""
+    if a.associate == "tracks":
+        with open(a.tracks, "rb") as f:
+            tracks = pickle.load(f, encoding="bytes")
+        relations = video.associate_tracks(video.from_frame_results(results, index, tracks), tracks, a.max_gap,
+                                           device=None if a.cpu else "cuda:0", frame_to_video=index)
+        mode = " along tracks (max_gap %d, %d gap frames bridged)" % (a.max_gap, video.gap_frames(relations))
+    else:
+        relations = video.associate(video.from_frame_results(results, index), device=None if a.cpu else "cuda:0")
     out = os.path.join(out_dir, "video_relations.json")
     with open(out, "w") as f:
         json.dump(relations, f)
-    print("association: %d videos, %d relations, %.1f ms; wrote %s" % (
-        len(relations), sum(len(r) for r in relations.values()), 1e3 * (time.time() - t0), out))
+    print("association%s: %d videos, %d relations, %.1f ms; wrote %s" % (
+        mode, len(relations), sum(len(r) for r in relations.values()), 1e3 * (time.time() - t0), out))
     if a.save_videofeat_path:
         t0 = time.time()
         pooled = rf.pool(relations, sink.arena, device=None if a.cpu else "cuda:0")
