@@ -96,6 +96,8 @@ SIGNATURES = {
     "i2v_video_viou_match": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _l, _i, _i, C.c_double, _p, _p, _p, _p, _z, _p]),
     "i2v_seqnms_workspace_bytes": (_z, [_i, _i, _i]),
     "i2v_seqnms": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, C.c_double, C.c_double, _i, _p, _p, _p, _p, _z, _p]),
+    "i2v_track_stitch_workspace_bytes": (_z, [_i, _i, _i, _i]),
+    "i2v_track_stitch": (_i, [_p] * 6 + [_i, _i, _i, _i, C.c_double, _i] + [_p] * 8 + [_p, _z, _p]),
     "i2v_relation_targets_workspace_bytes": (_z, [_i]),
     "i2v_relation_targets": (_i, [_p] * 11 + [_i] * 5 + [_p] * 10 + [_z, _p]),
     "i2v_recognition_rows_workspace_bytes": (_z, [_i]),

@@ -1,5 +1,5 @@
 """torch-facing wrappers of the packed-table ops: the evaluation and target kernels that read flat arrays and offset tables
-(csrc/seqnms.hip, video.hip, det_eval.hip, recognition.hip, relation_features.hip, relation_targets.hip, image_relations.hip,
+(csrc/seqnms.hip, track_stitch.hip, video.hip, det_eval.hip, recognition.hip, relation_features.hip, relation_targets.hip, image_relations.hip,
 proposal_eval.hip;
 csrc/table_common.h is what those share, ``packing.py`` what their host packers share).  ``ops`` re-exports the public names.
 
@@ -171,6 +171,40 @@ def seq_nms(group_off, frame_no, box_off, box, score, link_iou=0.5, nms_iou=0.3,
     if G > 0:
         _status(ws, 0, "seq_nms", "group")
     return tid, new_score, n_tracks
+
+
+def track_stitch(group_off, frame_no, box_off, box, score, tid, max_gap=3, stitch_iou=0.3, rescore="avg", device=None):
+    """The stitching step after Seq-NMS for a packed batch of groups (include/i2vsgg_hip.h, i2v_track_stitch;
+    ``seqnms.stitch_arrays_host`` states the rules and is the numpy form).  Arrays or tensors: ``seq_nms``'s tables (score: the
+    original scores) and its ``tid`` (N) int32; ``max_gap`` an int in [1, 7].  Returns device tensors (tid2 (N) int32, score2
+    (N) fp32, n_tracks2 (G) int32, fill_off (G+1) int32, fill_slot (M) int32, fill_tid (M) int32, fill_box (M,4) fp32,
+    fill_score (M) fp32), M = fill_off[G] new rows; a malformed group raises ``I2VError`` naming it."""
+    dev = _device(device, "seqnms.stitch_arrays_host")
+    if rescore not in ("avg", "max"):
+        raise ValueError("track_stitch: rescore is 'avg' or 'max' (got %r)" % (rescore,))
+    if isinstance(max_gap, bool) or int(max_gap) != max_gap:
+        raise ValueError("track_stitch: max_gap is an int in [1, 7] (got %r)" % (max_gap,))
+    group_off, frame_no, box_off, tid = (t.reshape(-1) for t in _stage(dev, torch.int32, group_off, frame_no, box_off, tid))
+    box, score = _stage(dev, torch.float32, box, score)
+    G, F, N, max_gap = group_off.numel() - 1, frame_no.numel(), score.numel(), int(max_gap)
+    if G < 0 or box_off.numel() != F + 1 or box.numel() != 4 * N or tid.numel() != N:
+        raise ValueError("track_stitch: array sizes do not agree")
+    rows = max(max_gap, 0) * N                                   # the bound the entry point states; M of them are written
+    tid2, score2 = tid.clone(), score.clone()                    # what a malformed group keeps
+    n_tracks2 = torch.zeros((G,), device=dev, dtype=torch.int32)
+    fill_off = torch.zeros((G + 1,), device=dev, dtype=torch.int32)
+    fill_slot, fill_tid = (torch.zeros((rows,), device=dev, dtype=torch.int32) for _ in range(2))
+    fill_box, fill_score = torch.zeros((rows, 4), device=dev), torch.zeros((rows,), device=dev)
+    ws = _launch(dev, "track_stitch", lambda *tail: lib.i2v_track_stitch(
+        ptr(group_off), ptr(frame_no), ptr(box_off), ptr(box), ptr(score), ptr(tid), G, F, N, max_gap, float(stitch_iou),
+        1 if rescore == "max" else 0, ptr(tid2), ptr(score2), ptr(n_tracks2), ptr(fill_off), ptr(fill_slot), ptr(fill_tid),
+        ptr(fill_box), ptr(fill_score), *tail), lib.i2v_track_stitch_workspace_bytes(G, F, N, max_gap), "track_stitch")
+    if G == 0:
+        return tid2, score2, n_tracks2, fill_off, fill_slot[:0], fill_tid[:0], fill_box[:0], fill_score[:0]
+    _status(ws, 0, "track_stitch", "group", "the tables are out of range, the frame numbers do not ascend or a track id is repeated "
+            "in a slot, out of range or not one run, at")
+    M = int(fill_off[G].item())
+    return tid2, score2, n_tracks2, fill_off, fill_slot[:M], fill_tid[:M], fill_box[:M], fill_score[:M]
 
 
 def relation_targets(det_off, det_box, det_cls, gt_off, gt_box, gt_cls, rel_off, rel, u, ih, iw, n_rel, device=None, read_status=True):

@@ -291,6 +291,29 @@ int32_t i2v_seqnms(const int32_t* group_off, const int32_t* frame_no, const int3
                    const float* score, int32_t n_groups, int32_t n_frames, int32_t n_boxes, double link_iou,
                    double nms_iou, int32_t rescore, int32_t* tid, float* new_score, int32_t* n_tracks,
                    void* workspace, size_t workspace_bytes, void* stream);
+/* Track stitching, the second step after Seq-NMS: tracklets joined across missed frames, the missed boxes interpolated
+ * (the rules are this project's own and are stated in full in i2vsgg_amd/seqnms.py, stitch_arrays_host).  The tables are
+ * i2v_seqnms's own (score: the ORIGINAL scores) plus its tid output; frame numbers ascend strictly within a group.  A
+ * tracklet is a (group, tid): one run of consecutive frame numbers.  Start boxes are visited in ascending (frame number,
+ * tid); each takes, among the end boxes of its group that have no successor yet, lie 1 .. max_gap missing frame numbers
+ * back and overlap it by >= stitch_iou (+1 convention), the one of largest overlap, then smaller gap, then lower tid.
+ * max_gap lies in [1, 7] (checked before the launch, without a device).  Outputs: tid2 (n_boxes; the chains numbered per
+ * group by the number of chain roots with a lower tid; -1 stays -1), score2 (n_boxes; rescore 0: the fp64 sum of the
+ * chain's original scores in frame order / their number, rounded to fp32; 1: their maximum; a box without tid keeps its
+ * score), n_tracks2 (n_groups), and the interpolated rows, grouped by group in fill_off (n_groups+1) order, within a group
+ * in link order, then ascending frame: fill_slot (the slot of frame_no the row belongs to), fill_tid, fill_box (x 4 fp32:
+ * a + (b - a) * (double(f - e) / double(s - e)) per coordinate in fp64, rounded), fill_score.  The four fill arrays hold
+ * max_gap * n_boxes rows (a bound: a link adds at most max_gap rows and a box starts at most one tracklet), of which the
+ * first fill_off[n_groups] are written.  One workgroup of one wave per group, persistent over its slots; no
+ * floating-point atomics.  Status word: 0, or 1 + the index of a group whose table entries were out of range, whose frame
+ * numbers do not ascend, that holds a tid twice in one slot, a tid outside [-1, boxes of the group) or a tid that is not
+ * one run (nothing is written for such a group; its n_tracks2 is 0 and it has no rows).  n_groups == 0 launches nothing. */
+size_t  i2v_track_stitch_workspace_bytes(int32_t n_groups, int32_t n_frames, int32_t n_boxes, int32_t max_gap);
+int32_t i2v_track_stitch(const int32_t* group_off, const int32_t* frame_no, const int32_t* box_off, const float* box,
+                         const float* score, const int32_t* tid, int32_t n_groups, int32_t n_frames, int32_t n_boxes,
+                         int32_t max_gap, double stitch_iou, int32_t rescore, int32_t* tid2, float* score2,
+                         int32_t* n_tracks2, int32_t* fill_off, int32_t* fill_slot, int32_t* fill_tid, float* fill_box,
+                         float* fill_score, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- rel_det training targets: relation-head rows from detected boxes (faster_rcnn_SGG_emb.py:476-578) -------------
  * The reference's branch does not run as shipped; what it means to compute is restated, with the exact rules, in
