@@ -94,6 +94,8 @@ SIGNATURES = {
     "i2v_video_associate_tracks": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _z, _p]),
     "i2v_video_viou_match_workspace_bytes": (_z, [_i, _i]),
     "i2v_video_viou_match": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _l, _i, _i, C.c_double, _p, _p, _p, _p, _z, _p]),
+    "i2v_video_relation_nms_workspace_bytes": (_z, [_i, _i]),
+    "i2v_video_relation_nms": (_i, [_p, _p, _p, _i, _i, _l, C.c_double, _p, _p, _p, _p, _p, _z, _p]),
     "i2v_seqnms_workspace_bytes": (_z, [_i, _i, _i]),
     "i2v_seqnms": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, C.c_double, C.c_double, _i, _p, _p, _p, _p, _z, _p]),
     "i2v_track_stitch_workspace_bytes": (_z, [_i, _i, _i, _i]),

@@ -27,7 +27,7 @@ from ._lib import need_cuda as _need_cuda
 from .conv_route import ARENA, AS_WGRAD, DIRECT, WINOGRAD, WINOGRAD_V
 from .table_ops import (det_eval_curve, det_eval_match, image_relation_count, image_relation_match, proposal_cover,  # noqa: F401
                         recognition_align, recognition_rows, relation_feature_pool, relation_targets, relation_topk, seq_nms, track_stitch, video_associate,
-                        video_associate_tracks, video_viou_match)
+                        video_associate_tracks, video_relation_nms, video_viou_match)
 
 _CL = torch.channels_last
 

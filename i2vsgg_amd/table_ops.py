@@ -1,5 +1,5 @@
 """torch-facing wrappers of the packed-table ops: the evaluation and target kernels that read flat arrays and offset tables
-(csrc/seqnms.hip, track_stitch.hip, video.hip, det_eval.hip, recognition.hip, relation_features.hip, relation_targets.hip, image_relations.hip,
+(csrc/seqnms.hip, track_stitch.hip, video.hip, video_nms.hip, det_eval.hip, recognition.hip, relation_features.hip, relation_targets.hip, image_relations.hip,
 proposal_eval.hip;
 csrc/table_common.h is what those share, ``packing.py`` what their host packers share).  ``ops`` re-exports the public names.
 
@@ -148,6 +148,33 @@ def video_viou_match(pred_off, pred_rel, pred_score, gt_off, gt_rel, boxes, viou
     if V > 0 and NP > 0:
         _status(ws, 0, "video_viou_match")
     return ov, hit, hit_ov
+
+
+def video_relation_nms(cell_off, rel, boxes, viou_threshold, device=None, read_status=True):
+    """Greedy suppression of duplicate video relations by trajectory overlap, every (video, triplet) cell of a packed batch
+    in one launch (include/i2vsgg_hip.h, i2v_video_relation_nms; ``video.pack_nms`` builds the arrays, ``video.suppress`` states
+    the rules and ``video.suppress_arrays_host`` is the numpy form).  Arrays or tensors: cell_off (C+1) int32, rel (R,10) int32
+    (the matcher's relation row, a cell's rows in rank order), boxes (n_boxes,4) fp64; ``viou_threshold`` in [0, 1].  Returns
+    device tensors (keep (R) int32, by (R) int32, by_ov (R) fp64, vol (R,2) fp64).  A malformed cell raises ``I2VError`` naming
+    it; ``read_status=False`` returns what the kernel wrote for the well-formed cells instead (a malformed cell's rows stay
+    keep 0, by -1, by_ov -1.0, vol 0.0)."""
+    dev = _device(device, "video.suppress(device=None)")
+    cell_off, rel = _stage(dev, torch.int32, cell_off, rel)
+    boxes, = _stage(dev, torch.float64, boxes)
+    C, R, NB = cell_off.numel() - 1, rel.numel() // 10, boxes.numel() // 4
+    if C < 0 or rel.numel() != 10 * R or boxes.numel() != 4 * NB:
+        raise ValueError("video_relation_nms: array sizes do not agree")
+    keep = torch.zeros((R,), device=dev, dtype=torch.int32)
+    by = torch.full((R,), -1, device=dev, dtype=torch.int32)
+    by_ov = torch.full((R,), -1.0, device=dev, dtype=torch.float64)
+    vol = torch.zeros((R, 2), device=dev, dtype=torch.float64)
+    ws = _launch(dev, "video_relation_nms", lambda *tail: lib.i2v_video_relation_nms(
+        ptr(cell_off), ptr(rel), ptr(boxes), C, R, NB, float(viou_threshold), ptr(keep), ptr(by), ptr(by_ov), ptr(vol), *tail),
+        lib.i2v_video_relation_nms_workspace_bytes(C, R), "video")
+    if read_status and C > 0 and R > 0:
+        _status(ws, 0, "video_relation_nms", "cell", "the tables are out of range, a cell holds more than 4096 relations or a "
+                "trajectory disagrees with its duration, at")
+    return keep, by, by_ov, vol
 
 
 def seq_nms(group_off, frame_no, box_off, box, score, link_iou=0.5, nms_iou=0.3, rescore="avg", device=None):

@@ -15,6 +15,10 @@ and the gather, and both do their arithmetic in float64 in the same operation or
 of their subject and object instead of by box overlap and may bridge up to ``max_gap`` frames.  Its rules are this project's
 own and stand in its docstring; it has its own packer, host form, kernel and gather and shares nothing with ``associate`` but
 the constants.
+
+``suppress`` is the step between either association and the per-video cap: duplicate relations of one triplet are suppressed
+greedily by the overlap of their trajectories (csrc/video_nms.hip, or the same rules in numpy).  It is off unless a caller asks
+for it; its rules stand in its docstring.
 """
 import numpy as np
 
@@ -148,6 +152,12 @@ def _iou(a, b):
     return np.where((left >= right) | (down <= up), 0.0, iou)
 
 
+def _check_cap(max_per_video):
+    if isinstance(max_per_video, bool) or not isinstance(max_per_video, (int, np.integer)) or max_per_video < 0:
+        raise ValueError("video: max_per_video is an int >= 0 (got %r)" % (max_per_video,))
+    return int(max_per_video)
+
+
 def _note(stats, key, value):
     if stats is not None and value < stats.get(key, np.inf):
         stats[key] = float(value)
@@ -239,16 +249,16 @@ def associate_arrays_host(pk, stats=None):
     return rel_id, rel_start, rel_len, rel_score, n_rel
 
 
-def gather_relations(pk, rel_id, rel_start, rel_len, rel_score, n_rel, names=None):
+def gather_relations(pk, rel_id, rel_start, rel_len, rel_score, n_rel, names=None, max_per_video=MAX_PER_VIDEO):
     """Per video: drop relations of fewer than 10 members, order the rest by score (descending, stable in creation order),
-    keep 200, and collect each one's trajectories and ``rel_idex`` from its members."""
+    keep ``max_per_video`` (200), and collect each one's trajectories and ``rel_idex`` from its members."""
     out = {}
     for v, vid in enumerate(pk.vids):
         f0, f1 = int(pk.frame_off[v]), int(pk.frame_off[v + 1])
         base, end = int(pk.pred_off[f0]), int(pk.pred_off[f1])
         nr = int(n_rel[v])
         keep = np.nonzero(rel_len[base:base + nr] >= MIN_MEMBERS)[0]
-        keep = keep[np.argsort(-rel_score[base + keep], kind="stable")][:MAX_PER_VIDEO]
+        keep = keep[np.argsort(-rel_score[base + keep], kind="stable")][:_check_cap(max_per_video)]
         ids = rel_id[base:end]
         by_rel = np.argsort(ids, kind="stable")                  # members of a relation, in frame order
         first = np.searchsorted(ids[by_rel], np.arange(nr + 1))
@@ -269,11 +279,12 @@ def gather_relations(pk, rel_id, rel_start, rel_len, rel_score, n_rel, names=Non
     return out
 
 
-def associate(frame_relations, device=None, names=None, stats=None):
+def associate(frame_relations, device=None, names=None, stats=None, max_per_video=MAX_PER_VIDEO):
     """``frame_relations``: {vid: [[fno, [[conf, [s, p, o], [sub_box, obj_box], rel_idex], ...]], ...]}.  Returns {vid:
     [{triplet, score, duration, sub_traj, obj_traj, rel_idex}, ...]}, at most 200 per video in descending score; triplets
     as ids, or as names with ``names=(objects, predicates)``.  ``device``: all videos in one kernel launch on that GPU;
-    None: the host implementation."""
+    None: the host implementation.  ``max_per_video``: the cap, for a caller that wants the pool ``suppress`` reads instead of
+    the final 200."""
     pk = pack_frames(frame_relations)
     if device is None:
         res = associate_arrays_host(pk, stats)
@@ -281,7 +292,7 @@ def associate(frame_relations, device=None, names=None, stats=None):
         from . import ops
         res = [t.cpu().numpy() for t in ops.video_associate(pk.frame_off, pk.frame_no, pk.pred_off, pk.score, pk.triplet,
                                                             pk.boxes, device=device)]
-    return gather_relations(pk, *res, names=names)
+    return gather_relations(pk, *res, names=names, max_per_video=max_per_video)
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -474,16 +485,17 @@ def associate_tracks_arrays_host(pk, max_gap=0):
     return rel_id, rel_start, rel_end, rel_len, rel_score, n_rel
 
 
-def gather_track_relations(pk, rel_id, rel_start, rel_end, rel_len, rel_score, n_rel, names=None):
+def gather_track_relations(pk, rel_id, rel_start, rel_end, rel_len, rel_score, n_rel, names=None, max_per_video=MAX_PER_VIDEO):
     """Per video: drop relations of fewer than 10 members, order the rest by score (descending, stable in creation order),
-    keep 200, and read each one's trajectories and pair indices from its two tracks' boxes, for every frame of the duration."""
+    keep ``max_per_video`` (200), and read each one's trajectories and pair indices from its two tracks' boxes, for every frame
+    of the duration."""
     out = {}
     for v, vid in enumerate(pk.vids):
         f0, f1 = int(pk.frame_off[v]), int(pk.frame_off[v + 1])
         base, end = int(pk.pred_off[f0]), int(pk.pred_off[f1])
         nr = int(n_rel[v])
         keep = np.nonzero(rel_len[base:base + nr] >= MIN_MEMBERS)[0]
-        keep = keep[np.argsort(-rel_score[base + keep], kind="stable")][:MAX_PER_VIDEO]
+        keep = keep[np.argsort(-rel_score[base + keep], kind="stable")][:_check_cap(max_per_video)]
         ids = rel_id[base:end]
         by_rel = np.argsort(ids, kind="stable")                  # members of a relation, in frame order
         first = np.searchsorted(ids[by_rel], np.arange(nr + 1))
@@ -525,7 +537,7 @@ def gap_frames(relations):
     return sum(r["duration"][1] - r["duration"][0] - r["members"] for rels in relations.values() for r in rels)
 
 
-def associate_tracks(frame_relations, tracks, max_gap=0, device=None, names=None, frame_to_video=None):
+def associate_tracks(frame_relations, tracks, max_gap=0, device=None, names=None, frame_to_video=None, max_per_video=MAX_PER_VIDEO):
     """Association along the object tracks that Seq-NMS computed: a second mode beside ``associate`` for boxes that carry a
     track id.  ``associate`` rediscovers identity frame by frame from box overlaps; here identity is given, so two objects of
     one class that pass each other keep their relations, and a relation that leaves its frames' top 100 for a few frames
@@ -566,7 +578,8 @@ def associate_tracks(frame_relations, tracks, max_gap=0, device=None, names=None
     Score: the float64 sum of the members' scores in member order, from the first member's score, divided by the number of
     members.  Gap frames are not members: they enter neither the mean nor the 10-member rule.
 
-    Selection as in ``gather_relations``: at least 10 members, descending score stable in creation order, the first 200.
+    Selection as in ``gather_relations``: at least 10 members, descending score stable in creation order, the first 200
+    (``max_per_video``).
 
     Output per relation: ``triplet``, ``score``, ``duration`` = [first member's frame, last member's frame + 1), ``sub_traj`` /
     ``obj_traj`` (the tracks' boxes from the pickle for EVERY frame of the duration), ``rel_idex`` (per frame of the duration the
@@ -583,7 +596,7 @@ def associate_tracks(frame_relations, tracks, max_gap=0, device=None, names=None
         from . import ops
         res = [t.cpu().numpy() for t in ops.video_associate_tracks(pk.frame_off, pk.frame_no, pk.pred_off, pk.score, pk.key, pk.since,
                                                                    max_gap, device=device)]
-    return gather_track_relations(pk, *res, names=names)
+    return gather_track_relations(pk, *res, names=names, max_per_video=max_per_video)
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -597,23 +610,26 @@ class PackedEval(object):
         self.gt_off, self.gt_rel, self.boxes = gt_off, gt_rel, boxes
 
 
+def _rel_rows(v, rels, vocab, boxes, n_box):
+    """The relation rows (REL_COLS int32 each) of the relations ``rels`` of video index ``v``; their trajectories are appended
+    to the list ``boxes`` (``n_box[0]`` counts its rows) and the triplets' elements numbered through ``vocab``."""
+    out = np.zeros((len(rels), REL_COLS), np.int32)
+    for k, r in enumerate(rels):
+        out[k, 0] = v
+        out[k, 1:4] = [vocab.setdefault(x, len(vocab)) for x in r["triplet"]]
+        out[k, 4:6] = r["duration"]
+        for c, key in ((6, "sub_traj"), (8, "obj_traj")):
+            out[k, c], out[k, c + 1] = n_box[0], len(r[key])
+            if len(r[key]):
+                boxes.append(np.asarray(r[key], np.float64).reshape(-1, 4))
+                n_box[0] += len(r[key])
+    return out
+
+
 def pack_eval(prediction, groundtruth):
     vocab = {}
     boxes, n_box = [], [0]
-
-    def rows(v, rels):
-        out = np.zeros((len(rels), REL_COLS), np.int32)
-        for k, r in enumerate(rels):
-            out[k, 0] = v
-            out[k, 1:4] = [vocab.setdefault(x, len(vocab)) for x in r["triplet"]]
-            out[k, 4:6] = r["duration"]
-            for c, key in ((6, "sub_traj"), (8, "obj_traj")):
-                out[k, c], out[k, c + 1] = n_box[0], len(r[key])
-                if len(r[key]):
-                    boxes.append(np.asarray(r[key], np.float64).reshape(-1, 4))
-                    n_box[0] += len(r[key])
-        return out
-
+    rows = lambda v, rels: _rel_rows(v, rels, vocab, boxes, n_box)
     vids, pred_off, gt_off, pred_rel, gt_rel, score = [], [0], [0], [], [], []
     for vid, gts in groundtruth.items():
         if len(gts) == 0:                                # the reference skips a video without ground truth
@@ -758,3 +774,226 @@ def evaluate(prediction, groundtruth, viou_threshold=0.5, det_nreturns=(50, 100)
     rec_at_n = dict((n, np.float32(tp_at[n]) / np.maximum(n_gt_total, np.finfo(np.float32).eps)) for n in det_nreturns)
     mprec_at_n = dict((n, np.mean(prec_at[n])) for n in tag_nreturns)
     return mean_ap, rec_at_n, mprec_at_n
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# relation NMS: duplicate relations suppressed by trajectory overlap, between the association and the per-video cap
+# ------------------------------------------------------------------------------------------------------------------
+NMS_POOL = 2048              # candidates of one video that take part by default
+NMS_MAX_POOL = 4096          # the most they can be (csrc/video_nms.hip RN_MAXCELL: a cell is at most a video's candidates)
+NMS_MAX_FRAMES = 1 << 20     # frames of one trajectory (RN_MAXLEN)
+
+
+class PackedNMS(object):
+    """Flat arrays of the candidates of a batch of videos (the layout of ``ops.video_relation_nms``): ``rel`` (R, 10) the
+    matcher's relation row, ``boxes`` (n_boxes, 4) float64, ``cell_off`` (C+1) the cells' rows, ``score`` (R).  For the way
+    back: ``video_off`` (V+1; a video's candidates are contiguous), ``src`` (R; the relation's index in its video's input
+    list), ``rank`` (R; its rank among its video's candidates) and ``n_input`` (V; relations the video came with)."""
+
+    def __init__(self, vids, video_off, cell_off, rel, score, boxes, src, rank, n_input):
+        self.vids, self.video_off, self.cell_off, self.rel, self.score, self.boxes = vids, video_off, cell_off, rel, score, boxes
+        self.src, self.rank, self.n_input = src, rank, n_input
+
+
+def _check_threshold(viou_threshold):
+    t = float(viou_threshold)
+    if not 0.0 <= t <= 1.0:
+        raise ValueError("video.suppress: the vIoU threshold lies in [0, 1] (got %r)" % (viou_threshold,))
+    return t
+
+
+def _check_relation(vid, k, r):
+    """What ``suppress`` states about one relation, or ``ValueError`` naming the video and the relation's index."""
+    def refuse(why):
+        raise ValueError("video.pack_nms: video %r relation %d: %s" % (vid, k, why))
+    try:
+        fstart, fend = (int(x) for x in r["duration"])
+        score = float(r["score"])
+        trajs = [np.asarray(r[key], np.float64) for key in ("sub_traj", "obj_traj")]
+    except (TypeError, ValueError, KeyError) as e:
+        refuse("not a relation (%s)" % (e,))
+    if not np.isfinite(score):
+        refuse("its score is not finite")
+    for name, b in zip(("sub_traj", "obj_traj"), trajs):
+        if b.size % 4 or (b.ndim != 2 and b.size):
+            refuse("%s is not a list of boxes [x1, y1, x2, y2]" % name)
+        b = b.reshape(-1, 4)
+        if len(b) != fend - fstart:
+            refuse("%s holds %d boxes for the duration [%d, %d)" % (name, len(b), fstart, fend))
+        if len(b) > NMS_MAX_FRAMES:
+            refuse("%s holds more than 2^20 frames" % name)
+        if not np.isfinite(b).all():
+            refuse("%s holds a box that is not finite" % name)
+        if (b[:, 2] < b[:, 0]).any() or (b[:, 3] < b[:, 1]).any():
+            refuse("%s holds a box with x2 < x1 or y2 < y1" % name)
+
+
+def pack_nms(prediction, pool=NMS_POOL):
+    """The tables of ``suppress`` (which states the rules) for {vid: [relation, ...]}: every video of ``prediction`` takes part,
+    in its order, also one without relations.  Every relation is checked, also one the pool drops."""
+    if isinstance(pool, bool) or not isinstance(pool, (int, np.integer)) or not 1 <= pool <= NMS_MAX_POOL:
+        raise ValueError("video.pack_nms: pool is an int in [1, %d] (got %r)" % (NMS_MAX_POOL, pool))
+    vocab, boxes, n_box = {}, [], [0]
+    vids, video_off, cells, rows, score, src, rank, n_input = [], [0], [], [], [], [], [], []
+    for v, (vid, rels) in enumerate(prediction.items()):
+        for k, r in enumerate(rels):
+            _check_relation(vid, k, r)
+        s = np.asarray([float(r["score"]) for r in rels], np.float64).reshape(-1)
+        order = np.argsort(-s, kind="stable")[:int(pool)]          # (score descending, input index ascending)
+        by_cell = {}                                             # insertion order: the rank of a cell's first member
+        for q, k in enumerate(order.tolist()):
+            by_cell.setdefault(tuple(rels[k]["triplet"]), []).append(q)
+        packed = [q for members in by_cell.values() for q in members]
+        vids.append(vid)
+        n_input.append(len(rels))
+        cells.extend(len(members) for members in by_cell.values())
+        rows.append(_rel_rows(v, [rels[order[q]] for q in packed], vocab, boxes, n_box))
+        score.append(s[order[packed]])
+        src.append(order[packed])
+        rank.append(np.asarray(packed, np.int64))
+        video_off.append(video_off[-1] + len(packed))
+    return PackedNMS(vids, np.asarray(video_off, np.int32), offsets(cells, "video.pack_nms: more than 2^31 relations"),
+                     cat(rows, (REL_COLS,), np.int32), cat(score, (), np.float64), cat(boxes, (4,), np.float64),
+                     cat(src, (), np.int64), cat(rank, (), np.int64), np.asarray(n_input, np.int64))
+
+
+def _check_nms_cell(pk, c):
+    """What the kernel reports through its status word raises here, naming the cell."""
+    rel, R, NB = pk.rel, len(pk.rel), len(pk.boxes)
+    r0, r1 = int(pk.cell_off[c]), int(pk.cell_off[c + 1])
+    bad = r0 < 0 or r1 < r0 or r1 > R or r1 - r0 > NMS_MAX_POOL
+    if not bad:
+        m = rel[r0:r1].astype(np.int64)
+        for c0 in (6, 8):
+            off, ln = m[:, c0], m[:, c0 + 1]
+            bad = bad or bool(((off < 0) | (ln < 0) | (off + ln > NB) | (ln != m[:, 5] - m[:, 4]) | (ln > NMS_MAX_FRAMES)).any())
+    if bad:
+        raise ValueError("video.suppress: cell %d is malformed: its offsets are out of range, it holds more than %d relations or a "
+                         "trajectory disagrees with its duration" % (c, NMS_MAX_POOL))
+    return r0, r1
+
+
+def _volumes(rel, boxes):
+    """vol (R, 2): per trajectory the sum of its boxes' +1 areas, the frames in order from 0.0, one accumulator each (a loop
+    over frames, vectorised over trajectories)."""
+    vol = np.zeros((len(rel), 2))
+    for which in (0, 1):
+        off, ln = rel[:, 6 + 2 * which].astype(np.int64), rel[:, 7 + 2 * which].astype(np.int64)
+        acc = np.zeros(len(rel))
+        for f in range(int(ln.max()) if len(ln) else 0):
+            m = np.nonzero(ln > f)[0]
+            b = boxes[off[m] + f]
+            acc[m] = acc[m] + ((b[:, 2] - b[:, 0]) + 1.0) * ((b[:, 3] - b[:, 1]) + 1.0)
+        vol[:, which] = acc
+    return vol
+
+
+def _viou_row(rel, boxes, vol, i, js, which):
+    """vIoU of trajectory ``which`` of row i with each of the rows js: the intersection over the common frames, ascending from
+    0.0, one accumulator per pair (a loop over frames, vectorised over pairs); 0 where the durations share no frame."""
+    m = rel[js].astype(np.int64)
+    a0, a1 = int(rel[i, 4]), int(rel[i, 5])
+    lo, hi = np.maximum(a0, m[:, 4]), np.minimum(a1, m[:, 5])
+    cnt = np.maximum(hi - lo, 0)
+    xi, yj = int(rel[i, 6 + 2 * which]) + (lo - a0), m[:, 6 + 2 * which] + (lo - m[:, 4])
+    acc = np.zeros(len(js))
+    for f in range(int(cnt.max()) if len(cnt) else 0):
+        k = np.nonzero(cnt > f)[0]
+        x, y = boxes[xi[k] + f], boxes[yj[k] + f]
+        w = (np.minimum(x[:, 2], y[:, 2]) - np.maximum(x[:, 0], y[:, 0])) + 1.0
+        h = (np.minimum(x[:, 3], y[:, 3]) - np.maximum(x[:, 1], y[:, 1])) + 1.0
+        acc[k] = acc[k] + np.maximum(w, 0.0) * np.maximum(h, 0.0)
+    out = np.zeros(len(js))
+    k = cnt > 0
+    out[k] = acc[k] / ((vol[i, which] + vol[js[k], which]) - acc[k])
+    return out
+
+
+def suppress_arrays_host(pk, viou_threshold, stats=None):
+    """The rules of ``ops.video_relation_nms`` in numpy, on the same arrays, with the same outputs: (keep (R) int32, by (R)
+    int32, by_ov (R) float64, vol (R, 2) float64).  Like the kernel it compares only kept rows with the later rows that are
+    still alive.  ``stats``: the smallest relative margin of an ov it evaluated against the threshold (``ov``)."""
+    T = _check_threshold(viou_threshold)
+    R = len(pk.rel)
+    cells = [_check_nms_cell(pk, c) for c in range(len(pk.cell_off) - 1)]
+    keep, by, by_ov = np.zeros(R, np.int32), np.full(R, -1, np.int32), np.full(R, -1.0)
+    vol = np.zeros((R, 2))
+    for r0, r1 in cells:
+        vol[r0:r1] = _volumes(pk.rel[r0:r1], pk.boxes)
+    for r0, r1 in cells:
+        alive = np.ones(r1 - r0, bool)
+        for i in range(r1 - r0):
+            if not alive[i]:
+                continue
+            keep[r0 + i] = 1
+            js = r0 + i + 1 + np.nonzero(alive[i + 1:])[0]
+            if not len(js):
+                continue
+            ov = np.minimum(_viou_row(pk.rel, pk.boxes, vol, r0 + i, js, 0), _viou_row(pk.rel, pk.boxes, vol, r0 + i, js, 1))
+            _note(stats, "ov", np.abs(ov - T).min() / max(T, 1e-300))
+            hit = js[ov > T]                                     # strict: ov == T stays
+            alive[hit - r0] = False
+            by[hit], by_ov[hit] = r0 + i, ov[ov > T]
+    return keep, by, by_ov, vol
+
+
+def suppress(prediction, viou_threshold, max_per_video=MAX_PER_VIDEO, pool=NMS_POOL, device=None, stats=None):
+    """Suppress duplicate video relations by trajectory overlap: the step of a VidVRD-style pipeline between the association
+    and the per-video cap.  The association emits the same relation many times (every near-identical candidate of the
+    per-frame top 100 grows a chain of its own); the matcher lets each ground truth be detected once, so the duplicates fill
+    the cap and count as false positives.  ``prediction`` is {vid: [relation, ...]} as ``gather_relations`` /
+    ``gather_track_relations`` write it -- with ``max_per_video=pool`` there, so that this step sees the candidates before the
+    cap.  Returns (prediction', info): per video the SAME dict objects, filtered and ordered, and info[vid] = {"candidates",
+    "suppressed", "kept"} (kept: what is returned, after the cap).  The host form is the specification; the kernel
+    (csrc/video_nms.hip) follows it bit for bit.
+
+    Relation.  A dict with ``triplet``, ``score``, ``duration`` = [fstart, fend), ``sub_traj``, ``obj_traj``; any further key
+    (``rel_idex``, track ids, ...) passes through untouched.  ``len(sub_traj) == len(obj_traj) == fend - fstart``; boxes are
+    finite with x2 >= x1 and y2 >= y1; scores are finite; a trajectory holds at most 2^20 frames.  ``pack_nms`` raises
+    ``ValueError`` naming the video and the relation's index otherwise (the matcher clamps such rows; this op refuses them).
+    Boxes widen to float64 exactly, and every decision is float64.
+
+    Candidates.  Per video the ``pool`` best by (score descending, input index ascending); the rest are dropped.  ``pool``
+    defaults to 2048 and is at most 4096.  A cell is one (video, triplet).  Cells are ordered by the rank of their first member
+    and within a cell the packed order is the rank order: the kernel sorts nothing.
+
+    Overlap.  vol(t) is the sum over the trajectory's frames, in frame order from 0.0 with one accumulator, of ((x2 - x1) + 1) *
+    ((y2 - y1) + 1).  inter(a, b) is the sum over the common frames max(fstart) .. min(fend) - 1, ascending, from 0.0 with one
+    accumulator, of max(0, (min(x2) - max(x1)) + 1) * max(0, (min(y2) - max(y1)) + 1).  viou = inter / ((vol_a + vol_b) - inter);
+    ov = min(viou_subject, viou_object), and 0 where the durations share no frame.  This is the reference's ``viou``
+    (lib/utils.py:221-262).  The sums are sequential on purpose: one lane owns one pair and needs no reduction.
+
+    Suppression, greedy as in nms_cpu.py and Seq-NMS.  A cell is gone through in rank order; a relation that no kept relation
+    suppresses is kept; a kept relation i suppresses every later j of its cell with ov(i, j) > T.  The comparison is strict:
+    ov == T stays.  T lies in [0, 1].  Per relation the outputs are ``keep`` (0 / 1), ``by`` (the packed index of the first
+    kept relation, in rank order, that suppresses it, or -1), ``by_ov`` (its ov with that relation, or -1.0) and ``vol`` (2
+    per relation).
+
+    Cap.  After suppression each video keeps its kept relations in descending score (stable) and takes the first
+    ``max_per_video`` (200).
+
+    ``device``: every cell of every video in one kernel launch on that GPU (``ops.video_relation_nms``); None: the host form
+    (``suppress_arrays_host``, which also fills ``stats``)."""
+    T = _check_threshold(viou_threshold)
+    cap = _check_cap(max_per_video)
+    pk = pack_nms(prediction, pool)
+    if device is None:
+        keep = suppress_arrays_host(pk, T, stats)[0]
+    else:
+        from . import ops
+        keep = ops.video_relation_nms(pk.cell_off, pk.rel, pk.boxes, T, device=device)[0].cpu().numpy()
+    out, info = {}, {}
+    for v, vid in enumerate(pk.vids):
+        p0, p1 = int(pk.video_off[v]), int(pk.video_off[v + 1])
+        kept = p0 + np.nonzero(keep[p0:p1])[0]
+        kept = kept[np.argsort(pk.rank[kept], kind="stable")]    # rank order: descending score, stable in input order
+        rels = prediction[vid]
+        out[vid] = [rels[int(pk.src[p])] for p in kept[:cap]]
+        info[vid] = {"candidates": p1 - p0, "suppressed": p1 - p0 - len(kept), "kept": len(out[vid])}
+    return out, info
+
+
+def nms_totals(info):
+    """The sums of ``suppress``'s info over the videos, as one line."""
+    tot = dict((key, sum(i[key] for i in info.values())) for key in ("candidates", "suppressed", "kept"))
+    return "relation NMS: %d videos, %d candidates, %d suppressed, %d kept" % (len(info), tot["candidates"], tot["suppressed"], tot["kept"])

@@ -267,6 +267,25 @@ int32_t i2v_video_viou_match(const int32_t* pred_off, const int32_t* pred_rel, c
                              int32_t n_videos, int32_t n_pred, int32_t n_gt, int64_t n_boxes, int32_t max_pred,
                              int32_t max_gt, double viou_threshold, double* ov, int32_t* hit, double* hit_ov,
                              void* workspace, size_t workspace_bytes, void* stream);
+/* Video relation NMS: duplicate relations of one (video, triplet) cell suppressed greedily by their trajectory overlap (the
+ * rules are stated in full in i2vsgg_amd/video.py, suppress; video.pack_nms builds the tables).  rel (n_rel x 10 int32) is
+ * the relation row above and boxes (n_boxes x 4 fp64) its trajectories; cell c owns rows [cell_off[c], cell_off[c+1]), at
+ * most 4096, already in rank order (descending score, equal scores in input order): nothing is sorted here.  For two rows
+ * of a cell ov = min(subject vIoU, object vIoU), 0 where the durations share no frame; vIoU = inter / ((vol_a + vol_b) -
+ * inter) with vol the sum over a whole trajectory, in frame order from 0.0, of ((x2 - x1) + 1) * ((y2 - y1) + 1) and inter
+ * the sum over the common frames, ascending from 0.0, of max(0, (min x2 - max x1) + 1) * max(0, (min y2 - max y1) + 1):
+ * fp64, one accumulator per sum, no reduction across lanes and no atomics.  A cell's rows are visited in order; a row that
+ * no kept row suppresses is kept, and a kept row i suppresses every later row j with ov(i, j) > viou_threshold (strict;
+ * the threshold lies in [0, 1], checked before the launch).  Outputs: keep (n_rel; 0 / 1), by (n_rel; the row index of the
+ * first kept row that suppresses it, or -1), by_ov (n_rel; its ov with that row, or -1.0) and vol (n_rel x 2: subject,
+ * object).  One workgroup per cell; only kept rows are compared, so no mask of all pairs is formed and the workspace holds
+ * the status word alone: 0, or 1 + the index of a malformed cell -- offsets out of range, more than 4096 rows, a trajectory
+ * outside `boxes`, longer than 2^20 frames or of a length that is not fend - fstart.  Nothing is written for such a cell.
+ * n_cells == 0 or n_rel == 0 launches nothing. */
+size_t  i2v_video_relation_nms_workspace_bytes(int32_t n_cells, int32_t n_rel);
+int32_t i2v_video_relation_nms(const int32_t* cell_off, const int32_t* rel, const double* boxes, int32_t n_cells,
+                               int32_t n_rel, int64_t n_boxes, double viou_threshold, int32_t* keep, int32_t* by,
+                               double* by_ov, double* vol, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- Seq-NMS: per-frame detections of one class linked into object tracks (Han et al., 2016) ---------------------
  * The stage between the detector's all_boxes and the boxes the relation loop reads; the reference ran it outside its

@@ -1315,13 +1315,80 @@ def gen_track_eval():
          hit=hits, hit_ov=ovs, margin_ov=np.asarray(m_ov), margin_ov_gap=np.asarray(m_gap), margin_bound=np.float64(MARGIN))
 
 
+# ----------------------------------------------------------------------------- video relation NMS
+def gen_video_nms():
+    """tests/golden/video_nms.npz: greedy suppression decided from the reference's own ``viou`` on the cases of
+    tests/video_nms_cases.py golden_case.  Per case the table of min(viou(subjects), viou(objects)) of EVERY same-triplet pair
+    comes from the reference's function; the greedy decisions (rank order, strict ``>``) are taken from that table by the loop
+    below.  The file holds data only, per case ``c<k>_``: the packed inputs (cell_off, rel, boxes, score), the threshold, the
+    seed the case ended on and keep / by / by_ov.  Integer boxes make every sum exact in any order, so the package's host form
+    must equal those cases in every bit; a fractional case with a decisive ov closer than 1e-9 (relative) to its threshold is
+    redrawn from the next seed -- never dropped."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import video_nms_cases as nc
+    from i2vsgg_amd import video
+    MARGIN = 1e-9
+    ref_viou = _utils_functions(["viou"])["viou"]
+    out, margins, redraws = {}, [], 0
+    for k in range(nc.GOLDEN_CASES):
+        integer = k < nc.GOLDEN_CASES - 2
+        seed = nc.GOLDEN_SEED + 100 * k
+        while True:
+            case = nc.golden_case(k, seed)
+            T = case.T
+            pk = video.pack_nms(case.prediction, case.pool)
+            rels = [case.prediction[vid][int(pk.src[p])] for v, vid in enumerate(pk.vids)
+                    for p in range(int(pk.video_off[v]), int(pk.video_off[v + 1]))]
+            R = len(rels)
+            keep, by, by_ov, margin, pairs = np.zeros(R, np.int32), np.full(R, -1, np.int32), np.full(R, -1.0), np.inf, 0
+            for c in range(len(pk.cell_off) - 1):
+                r0, r1 = int(pk.cell_off[c]), int(pk.cell_off[c + 1])
+                assert len(set(tuple(rels[i]["triplet"]) for i in range(r0, r1))) == 1
+                table = {}
+                for i in range(r0, r1):
+                    for j in range(i + 1, r1):
+                        a, b = rels[i], rels[j]
+                        table[i, j] = min(ref_viou(a["sub_traj"], a["duration"], b["sub_traj"], b["duration"]),
+                                          ref_viou(a["obj_traj"], a["duration"], b["obj_traj"], b["duration"]))
+                pairs += len(table)
+                gone = set()
+                for i in range(r0, r1):
+                    if i in gone:
+                        continue
+                    keep[i] = 1
+                    for j in range(i + 1, r1):
+                        if j not in gone:
+                            margin = min(margin, abs(table[i, j] - T) / max(T, 1e-300))
+                            if table[i, j] > T:
+                                gone.add(j)
+                                by[j], by_ov[j] = i, table[i, j]
+            if integer or margin >= MARGIN:
+                break
+            seed, redraws = seed + 1, redraws + 1
+        keep_h, by_h, by_ov_h, _ = video.suppress_arrays_host(pk, T)           # the package's host form must already agree
+        assert (keep_h == keep).all() and (by_h == by).all(), k
+        assert np.allclose(by_ov_h, by_ov, rtol=1e-12, atol=0), k
+        if integer:
+            assert (by_ov_h.view(np.int64) == by_ov.view(np.int64)).all(), k
+        print("    case %2d seed %d (%s): T %.3g, %3d relations in %d cells, %5d pairs, %3d kept, margin %.3g" % (
+            k, seed, "integer" if integer else "fractional", T, R, len(pk.cell_off) - 1, pairs, int(keep.sum()), margin))
+        margins.append(margin)
+        out.update({"c%d_cell_off" % k: pk.cell_off, "c%d_rel" % k: pk.rel, "c%d_boxes" % k: pk.boxes, "c%d_score" % k: pk.score,
+                    "c%d_T" % k: np.float64(T), "c%d_seed" % k: np.int64(seed), "c%d_keep" % k: keep, "c%d_by" % k: by,
+                    "c%d_by_ov" % k: by_ov})
+    assert min(margins[-2:]) >= MARGIN
+    print("    %d redraws; smallest margin of a fractional case %.3g" % (redraws, min(margins[-2:])))
+    save("video_nms", "extracted", n_cases=np.array(nc.GOLDEN_CASES), margin=np.asarray(margins), margin_bound=np.float64(MARGIN), **out)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--only", default="")
     a = ap.parse_args()
     os.makedirs(GOLD, exist_ok=True)
     todo = a.only.split(",") if a.only else ["direct", "roialign", "roialign_fresh", "tails", "rpn", "nets", "full", "ctx", "step",
-                                             "vrd", "video", "det_eval", "recognition", "video_relation_feat", "track_eval"]
+                                             "vrd", "video", "det_eval", "recognition", "video_relation_feat", "track_eval",
+                                             "video_nms"]
     if "direct" in todo:
         print("[direct imports]")
         gen_direct()
@@ -1355,6 +1422,9 @@ def main():
     if "track_eval" in todo:
         print("[trajectory mAP of object tracks: viou / eval_detection_scores of lib/utils.py compiled from their own lines]")
         gen_track_eval()
+    if "video_nms" in todo:
+        print("[video relation NMS: viou of lib/utils.py compiled from its own lines, the greedy loop taken from its table]")
+        gen_video_nms()
     if any(t in todo for t in ("rpn", "nets", "full", "vrd", "ctx", "step")):
         print("[imports with placeholders]")
         cfg = install_placeholders()

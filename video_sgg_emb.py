@@ -4,7 +4,8 @@
 relation instances on the GPU (``i2vsgg_amd.video.associate``) and written to ``video_relations.json`` beside ``relations.pkl``,
 the file ``eval_video_relations.py`` scores.  ``--associate tracks`` links along the track ids of the boxes the loop ran on
 instead (``i2vsgg_amd.video.associate_tracks``; ``--max_gap G`` lets a relation miss up to G frames, ``--tracks FILE`` names the box
-pickle, by default the loop's ``--target_gt_rels_path``).  ``--relations FILE`` skips the frame loop and starts from a pickle that an earlier
+pickle, by default the loop's ``--target_gt_rels_path``).  ``--rel_nms T`` suppresses duplicate relations by trajectory vIoU before the cap of
+200 (``i2vsgg_amd.video.suppress``; ``--rel_nms_pool N`` candidates per video).  ``--relations FILE`` skips the frame loop and starts from a pickle that an earlier
 run wrote.  The synthetic imdb has no video ids: ``--frames_per_video N`` takes the frames in the order of their paths (the
 loader's order depends on the frames' aspect ratios) and makes every N consecutive ones a video, numbered from 0 (default: the
 whole imdb is one video, frame number = index).  ``--save_videofeat_path DIR`` adds the hand-off to the video-level stage
@@ -48,7 +49,15 @@ def main(argv=None, hold=None):
                    "frames' top 100 and still go on")
     p.add_argument("--tracks", default="", help="with --associate tracks: the per-frame box pickle with tids (default: the frame "
                    "loop's --target_gt_rels_path; required with --relations)")
+    p.add_argument("--rel_nms", type=float, default=None, help="suppress duplicate relations: of two relations of one triplet whose "
+                   "subject and object trajectories both overlap by more than this vIoU the better one stays (video.suppress); the "
+                   "association then keeps --rel_nms_pool candidates per video and the cap of 200 comes after the suppression")
+    p.add_argument("--rel_nms_pool", type=int, default=0, help="with --rel_nms: candidates per video (default 2048, at most 4096)")
     a, rest = p.parse_known_args(argv)
+    if a.rel_nms is None and a.rel_nms_pool:
+        raise SystemExit("--rel_nms_pool belongs to --rel_nms: give it")
+    if a.rel_nms is not None and not 0.0 <= a.rel_nms <= 1.0:
+        raise SystemExit("--rel_nms lies in [0, 1] (got %r)" % a.rel_nms)
     if a.associate != "tracks" and (a.max_gap != 0 or a.tracks):
         raise SystemExit("--max_gap and --tracks belong to --associate tracks: give it")
     if a.associate == "tracks" and not 0 <= a.max_gap <= 7:
@@ -96,14 +105,22 @@ def main(argv=None, hold=None):
         print("wrote %s/semantic_embedding.npy and the features of %d frames" % (a.save_feat_path, n))
     t0 = time.time()
     mode = ""
+    pool = (a.rel_nms_pool or video.NMS_POOL) if a.rel_nms is not None else 0
+    if pool and not 1 <= pool <= video.NMS_MAX_POOL:
+        raise SystemExit("--rel_nms_pool lies in 1..%d (got %d)" % (video.NMS_MAX_POOL, pool))
+    cap = dict(max_per_video=pool) if pool else {}       # with --rel_nms the suppression sees the candidates before the cap
     if a.associate == "tracks":
         with open(a.tracks, "rb") as f:
             tracks = pickle.load(f, encoding="bytes")
         relations = video.associate_tracks(video.from_frame_results(results, index, tracks), tracks, a.max_gap,
-                                           device=None if a.cpu else "cuda:0", frame_to_video=index)
-        mode = " along tracks (max_gap %d, %d gap frames bridged)" % (a.max_gap, video.gap_frames(relations))
+                                           device=None if a.cpu else "cuda:0", frame_to_video=index, **cap)
     else:
-        relations = video.associate(video.from_frame_results(results, index), device=None if a.cpu else "cuda:0")
+        relations = video.associate(video.from_frame_results(results, index), device=None if a.cpu else "cuda:0", **cap)
+    if pool:
+        relations, info = video.suppress(relations, a.rel_nms, video.MAX_PER_VIDEO, pool, device=None if a.cpu else "cuda:0")
+        print(video.nms_totals(info) + " (vIoU %g)" % a.rel_nms)
+    if a.associate == "tracks":
+        mode = " along tracks (max_gap %d, %d gap frames bridged)" % (a.max_gap, video.gap_frames(relations))
     out = os.path.join(out_dir, "video_relations.json")
     with open(out, "w") as f:
         json.dump(relations, f)
