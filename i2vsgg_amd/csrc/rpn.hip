@@ -510,8 +510,14 @@ nms_scan_super_kernel(const unsigned long long* __restrict__ mask, int n, int nb
         int settled = 0;
         if (fixed_point) {
             __shared__ unsigned long long s_alive[SUPER_WORDS], s_keepw[SUPER_WORDS], s_supp[SUPER_WORDS];
-            __shared__ int s_changed;
+            // ``s_changed``: two slots, sweep s owns slot s & 1.  With one slot, cleared for sweep s + 1 before the first barrier of
+            // that sweep, a wave that had not yet read sweep s's verdict could see the cleared flag, call the super-block settled
+            // and meet the keep-list barrier while the others stood at the sweep's.  Now slot s & 1 is set (changed words) and slot
+            // (s + 1) & 1 cleared (thread 0) only between the two barriers of sweep s: the readers of the cleared slot, sweep s - 1's,
+            // have all passed the first of them, and the readers of the set slot come after the second.
+            __shared__ int s_changed[2];
             if (threadIdx.x < SUPER_WORDS) {
+                if (threadIdx.x < 2) s_changed[threadIdx.x] = 0;
                 const int rb = w0 + (int)threadIdx.x;
                 unsigned long long a = 0ull;
                 if (rb < nblk) {
@@ -534,16 +540,16 @@ nms_scan_super_kernel(const unsigned long long* __restrict__ mask, int n, int nb
                 acc |= __shfl_xor(acc, 16);
                 acc |= __shfl_xor(acc, 32);
                 if (lane < SUPER_WORDS && acc) atomicOr(&s_supp[w], acc);
-                if (threadIdx.x == 0) s_changed = 0;
                 __syncthreads();
                 if (threadIdx.x < SUPER_WORDS) {
                     const unsigned long long nk = s_alive[threadIdx.x] & ~s_supp[threadIdx.x];
-                    if (nk != s_keepw[threadIdx.x]) s_changed = 1;
+                    if (nk != s_keepw[threadIdx.x]) s_changed[sweep & 1] = 1;
                     s_keepw[threadIdx.x] = nk;
                     s_supp[threadIdx.x] = 0ull;
+                    if (threadIdx.x == 0) s_changed[(sweep + 1) & 1] = 0;
                 }
                 __syncthreads();
-                if (!s_changed) { settled = 1; break; }
+                if (!s_changed[sweep & 1]) { settled = 1; break; }
             }
             if (settled) {
                 // the keep list: rows in order, cut at the limit
