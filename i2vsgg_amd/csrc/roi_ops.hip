@@ -977,16 +977,12 @@ roi_pool_fwd_c128_kernel(const float* __restrict__ feat, const float* __restrict
         sarg[e] = mi.x; sarg[e + P] = mi.y; sarg[e + 2 * P] = mi.z; sarg[e + 3 * P] = mi.w;
     }
     __syncthreads();
-    if (out_nchw) {                      // (r, c0..c0+128, :, :) is contiguous: 16-byte rows when the chunk's base allows
-        float* o = out + (long long)r * C * P + (long long)c0 * P;
+    if (out_nchw) {                      // (r, c0..c0+128, :, :) is contiguous, in 16-byte rows: C and c0 are multiples of 128, so
+        float* o = out + (long long)r * C * P + (long long)c0 * P;       // the chunk starts and ends on a multiple of 128 * P elements
         int* a = argmax + (long long)r * C * P + (long long)c0 * P;
-        if ((((long long)r * C + c0) * P) % 4 == 0 && (128 * P) % 4 == 0) {
-            for (int e = threadIdx.x * 4; e < 128 * P; e += 4 * blockDim.x) {
-                *(float4*)(o + e) = *(const float4*)(sval + e);
-                *(int4*)(a + e) = *(const int4*)(sarg + e);
-            }
-        } else {
-            for (int e = threadIdx.x; e < 128 * P; e += blockDim.x) { o[e] = sval[e]; a[e] = sarg[e]; }
+        for (int e = threadIdx.x * 4; e < 128 * P; e += 4 * blockDim.x) {
+            *(float4*)(o + e) = *(const float4*)(sval + e);
+            *(int4*)(a + e) = *(const int4*)(sarg + e);
         }
     } else {                             // NHWC: (r, p, c) with c contiguous
         for (int e = threadIdx.x; e < 128 * P; e += blockDim.x) {

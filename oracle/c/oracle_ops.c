@@ -19,8 +19,12 @@
  *                       (the CPU twin roi_align.c:138-190 inverts its bounds test, :175) and held
  *                       to the transpose of the pinned forward, element by element
  *                       (tests/test_oracle_golden.py).
- *   roi_pool_*          UNPINNED: model._C source is absent from the reference tree;
- *                       restated from roi_pooling_kernel.cu:24-93,128-203.
+ *   roi_pool_*          pinned  : restated from roi_pooling_kernel.cu:24-93,128-203 (model._C source is absent from the
+ *                       reference tree) and held, through the numpy restatement of tests/roi_pool_ref.py (bit-equal
+ *                       to this one), to torch's adaptive_max_pool2d on the crop -- the same operation for a ROI
+ *                       inside the map, values and first-maximum argmax -- and, at the extents where the float32 bin
+ *                       rule parts from torch's integer one (57, 114, 121 cells over 7 bins; 7, 14, 28, ... over 13),
+ *                       to hand-derived answers (tests/test_roi_pool_ref_host.py).
  *   roi_align_sampled_* UNPINNED: model._C (roi_layers/roi_align.py:20,:31) is the csrc of
  *                       facebookresearch/maskrcnn-benchmark via jwyang/faster-rcnn.pytorch
  *                       (pytorch-1.0 branch), no commit pinned, source absent from the

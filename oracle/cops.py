@@ -138,7 +138,9 @@ def roi_align_avg_bwd(gout, rois, feat_shape, scale):
 
 
 def roi_pool_fwd(feat, rois, ph, pw, scale):
-    """roi_pooling_kernel.cu:24-93 -> (out, argmax[plane index or -1]).  Parity unpinned."""
+    """roi_pooling_kernel.cu:24-93 -> (out, argmax[plane index or -1]).  Pinned: bit-equal to the numpy restatement of
+    tests/roi_pool_ref.py, which equals torch's adaptive_max_pool2d on the crop for every ROI inside the map and hand-derived
+    answers where the float32 bin rule reaches a cell past torch's integer one (tests/test_roi_pool_ref_host.py)."""
     feat, pf = _f(feat)
     rois, pr = _f(rois)
     B, C, H, W = feat.shape

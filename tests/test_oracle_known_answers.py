@@ -103,6 +103,23 @@ def test_roi_pool_hand_worked():
     exp = np.zeros((4, 6), np.float32)
     exp[1, 2] = exp[1, 4] = exp[3, 2] = exp[3, 4] = 1
     assert np.array_equal(gin[0, 0], exp)
+    # a tied window: 7 at (1,2), (1,4) and (2,1), zeros elsewhere (a post-ReLU map); the first cell in (h, w) order wins
+    # (`>` at :83, not `>=`) and takes the whole gradient
+    tied = np.zeros((1, 1, 4, 6), np.float32)
+    tied[0, 0, 1, 2] = tied[0, 0, 1, 4] = tied[0, 0, 2, 1] = 7
+    whole = np.array([[0, 0, 0, 5, 3]], np.float32)
+    out4, arg4 = cops.roi_pool_fwd(tied, whole, 1, 1, 1.0)
+    assert out4[0, 0, 0, 0] == 7 and arg4[0, 0, 0, 0] == 1 * 6 + 2
+    out4, arg4 = cops.roi_pool_fwd(tied, whole, 2, 1, 1.0)                         # rows 0-1: (1,2); rows 2-3: (2,1) alone
+    assert arg4[0, 0, :, 0].tolist() == [8, 13]
+    out4, arg4 = cops.roi_pool_fwd(np.zeros_like(tied), whole, 1, 1, 1.0)          # all equal: the window's first cell
+    assert out4[0, 0, 0, 0] == 0 and arg4[0, 0, 0, 0] == 0
+    gin = cops.roi_pool_bwd(np.full((1, 1, 1, 1), 3, np.float32), whole, arg4, tied.shape)
+    assert gin[0, 0, 0, 0] == 3 and gin.sum() == 3
+    # negative halves round away from zero too: x1 = y1 = -0.5 -> -1 (half-even: 0), x2 = 2.5 -> 3, y2 = 0.5 -> 1.  Five columns
+    # -1..3 over five bins: bin 0 is column -1, clamped away (0, -1); bin k is column k - 1 over rows 0..1, the maximum in row 1
+    out5, arg5 = cops.roi_pool_fwd(feat, np.array([[0, -0.5, -0.5, 2.5, 0.5]], np.float32), 1, 5, 1.0)
+    assert out5[0, 0, 0].tolist() == [0, 6, 7, 8, 9] and arg5[0, 0, 0].tolist() == [-1, 6, 7, 8, 9]
 
 
 def test_detection_postprocess_hand_worked():
