@@ -47,6 +47,9 @@ SIGNATURES = {
     "i2v_conv_split_workspace_bytes": (_z, [_i, _i, _i, _i, _i, _i, _i, _i, _i]),
     "i2v_conv_fwd_plan": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _z, _p, _i]),
     "i2v_conv_wgrad_plan": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _z, _p, _i]),
+    "i2v_roi_align_fwd_plan": (_i, [_i] * 10 + [_p, _i]),
+    "i2v_roi_align_bwd_plan": (_i, [_i] * 10 + [_p, _i]),
+    "i2v_nms_plan": (_i, [_i, _i, _p, _i]),
     "i2v_set_tuning": (_i, [_i, _i]),
     "i2v_get_tuning": (_i, [_i]),
     "i2v_gemm_nt_batched": (_i, [_p, _p, _p, _i, _i, _i, _i, _l, _l, _l, _p, _z, _p]),

@@ -7,10 +7,11 @@
 #include <stddef.h>
 #include <stdint.h>
 #include "../../include/i2vsgg_hip.h"
+#include "chip.h"
 
 namespace convplan {
 
-constexpr int NUM_CU = 256;
+using i2v::NUM_CU;
 constexpr int KTAB_MAX = 2560;  // filter-tap table entries (K/4): KH*KW*Cin <= 10240 for non-1x1 filters
 constexpr int BKS = 32;         // k per LDS stage of the forward/dgrad kernel (= floats per LDS row)
 constexpr int kSplitInKernelMax = 4;   // most splits the in-kernel split-K finish sums (else: atomics)

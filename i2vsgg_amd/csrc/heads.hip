@@ -399,12 +399,7 @@ extern "C" int32_t i2v_dpixel_fwd(const float* x, const float* w1, const float* 
     I2V_CHECK_ARG(!feat || M % pix_per_roi == 0, "dpixel_fwd: M must be a whole number of ROIs when feat is requested");
     if (M == 0) return I2V_OK;
     hipStream_t st = (hipStream_t)stream;
-    static bool attr = [] {
-        (void)hipFuncSetAttribute((const void*)dpixel_fwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, DP_LDS_FLOATS * 4);
-        (void)hipFuncSetAttribute((const void*)dpixel_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, DP_LDS_FLOATS * 4);
-        return true;
-    }();
-    (void)attr;
+    I2V_ALLOW_LDS("dpixel_fwd_kernel", DP_LDS_FLOATS * 4, dpixel_fwd_kernel);
     dpixel_fwd_kernel<<<i2v_cdiv(M, DP_ROWS), DP_THREADS, DP_LDS_FLOATS * 4, st>>>(x, w1, w2, w3, h1, h2, d, M);
     I2V_CHECK_LAUNCH("dpixel_fwd");
     if (feat) {
@@ -433,12 +428,7 @@ extern "C" int32_t i2v_dpixel_bwd(const float* gd, const float* gfeat, const flo
     float* w2t = w1t + 1024 * 512;
     dp_transpose_kernel<<<512, 256, 0, st>>>(w1, w1t, 512, 1024);
     dp_transpose_kernel<<<128, 256, 0, st>>>(w2, w2t, 128, 512);
-    static bool attr = [] {
-        (void)hipFuncSetAttribute((const void*)dpixel_fwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, DP_LDS_FLOATS * 4);
-        (void)hipFuncSetAttribute((const void*)dpixel_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, DP_LDS_FLOATS * 4);
-        return true;
-    }();
-    (void)attr;
+    I2V_ALLOW_LDS("dpixel_bwd_kernel", DP_LDS_FLOATS * 4, dpixel_bwd_kernel);
     dpixel_bwd_kernel<<<i2v_cdiv(M, DP_ROWS), DP_THREADS, DP_LDS_FLOATS * 4, st>>>(gd, gfeat, d, h1, h2, w1t, w2t, w3, g3,
                                                                                  gh2, gh1, gx, M, pix_per_roi, -lambda);
     I2V_CHECK_LAUNCH("dpixel_bwd");

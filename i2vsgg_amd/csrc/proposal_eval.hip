@@ -218,11 +218,8 @@ extern "C" int32_t i2v_proposal_cover(const int32_t* cand_off, const double* can
     I2V_CLEAR_STATUS(ws, 0, 4, st, "proposal_cover: clearing the status word failed");
     if (n_images == 0) return I2V_OK;
     const size_t lds = pe_lds_bytes(max_gt, max_cand);
-    if (lds > 48 * 1024 &&
-        hipFuncSetAttribute((const void*)proposal_cover_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-        i2v_set_error("proposal_cover: %zu bytes of LDS for one cell were refused", lds);
-        return I2V_ERR_LAUNCH;
-    }
+    // once, for the largest cell the entry accepts (just over the 64 KB a launch gets by default)
+    if (lds > 48 * 1024) I2V_ALLOW_LDS("proposal_cover_kernel", pe_lds_bytes(PE_MAXG, PE_MAXC), proposal_cover_kernel);
     proposal_cover_kernel<<<n_images * n_limits * n_areas, PE_THREADS, lds, st>>>(
         cand_off, cand_box, gt_off, gt_box, gt_area, limits, ranges, n_cand, n_gt, n_limits, n_areas, max_gt, max_cand, ov, cand,
         step, (int*)ws);

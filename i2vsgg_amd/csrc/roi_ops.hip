@@ -5,10 +5,17 @@
 //
 // Arithmetic follows roi_align/src/roi_align.c:91-134 exactly (float / double
 // promotion, one rounding per op; this file is built with -ffp-contract=off).
+//
+// Which RoIAlign kernel form a shape takes is roi_plan.h's decision; the RoIAlign entry points at the end of this file
+// check their arguments, ask for the plan and switch on it (ROIPool's launcher still decides for itself: DESIGN.md).
 #include "common.h"
+#include "chip.h"
+#include "roi_plan.h"
 #include <float.h>
+#include <algorithm>
 
 namespace {
+using namespace roiplan;
 
 struct Strides { long long b, c, h, w; };
 
@@ -357,9 +364,7 @@ __device__ inline AxisGeom ra_axis(float lo, float hi, float scale, int n, int A
     return g;
 }
 
-constexpr int RAB_SEG = 1024;           // (roi, sample row) pairs examined per list pass: 256 per wave
-constexpr int RAB_BATCH = 4;            // listed pairs whose sample gradients are staged in LDS together (one per wave's record lanes)
-constexpr int RAB_MAXA = 8;             // sample columns per row this kernel takes
+// RAB_SEG, RAB_BATCH, RAB_MAXA: roi_plan.h (they size the kernels' LDS)
 
 struct TapRec { int cell0; float w0; int cell1; float w1; };    // a sample column's tap on the even / odd cell: row-buffer cell, weight
 
@@ -1135,35 +1140,35 @@ extern "C" int32_t i2v_roi_align_fwd(const float* feat, int32_t feat_layout, int
     I2V_CHECK_ARG(avg == 0 || avg == 1, "roi_align_fwd: avg must be 0/1");
     I2V_CHECK_ARG(avg || (PH > 1 && PW > 1), "roi_align_fwd: aligned grid needs >=2 points per side");
     hipStream_t st = (hipStream_t)stream;
-    Strides os = out_strides(out_layout, C, PH, PW);
-    if (feat_layout == I2V_LAYOUT_NHWC && (C % 4) == 0) {
-        const int groups = (PW + 1) / 2;
-        // one ROI x 128 channels per workgroup (each tap through the L2 once): NHWC output, <= 64 sample points, 32-bit offsets;
-        // I2V_ROIALIGN_COLS = 1 keeps the column-pair kernel, 0 the round-1 row kernel
-        const bool per_roi = g_i2v_tuning[I2V_TUNE_ROIALIGN_COLS] == 2 && out_layout == I2V_LAYOUT_NHWC && (C % 128) == 0 &&
-                             (PH + avg) * (PW + avg) <= 64 && (long long)B * H * W * C * 4 < (1ll << 31);
-        if (per_roi) {
-            if (R * (C / 128) < 512) {          // a small launch: 64 channels per workgroup, one pass
-                if (avg) roi_align_fwd_roi_kernel<1, 64><<<R * (C / 64), 256, 0, st>>>(feat, rois, out, R, C, H, W, PH, PW, scale);
-                else roi_align_fwd_roi_kernel<0, 64><<<R * (C / 64), 256, 0, st>>>(feat, rois, out, R, C, H, W, PH, PW, scale);
-            } else if (avg) roi_align_fwd_roi_kernel<1><<<R * (C / 128), 256, 0, st>>>(feat, rois, out, R, C, H, W, PH, PW, scale);
-            else roi_align_fwd_roi_kernel<0><<<R * (C / 128), 256, 0, st>>>(feat, rois, out, R, C, H, W, PH, PW, scale);
-        } else if (!g_i2v_tuning[I2V_TUNE_ROIALIGN_COLS]) {
-            if (avg) roi_align_fwd_nhwc<1><<<R * PH, 256, 0, st>>>(feat, rois, out, C, H, W, PH, PW, scale, os);
-            else roi_align_fwd_nhwc<0><<<R * PH, 256, 0, st>>>(feat, rois, out, C, H, W, PH, PW, scale, os);
-        } else if (avg) {
-            roi_align_fwd_nhwc_cols<1><<<(R + 7) / 8 * 8 * PH * groups, 256, 0, st>>>(feat, rois, out, R, C, H, W, PH, PW, scale, os);
-        } else {
-            roi_align_fwd_nhwc_cols<0><<<(R + 7) / 8 * 8 * PH * groups, 256, 0, st>>>(feat, rois, out, R, C, H, W, PH, PW, scale, os);
-        }
-    } else {
-        Strides fs = feat_strides(feat_layout, C, H, W);
-        long long total = (long long)R * C * PH * PW;
-        int grid = (int)fmin((double)i2v_cdiv(total, 256), 65535.0 * 4);
-        if (avg) roi_align_fwd_generic<1><<<grid, 256, 0, st>>>(feat, rois, out, total, C, H, W, PH, PW, scale, fs, os);
-        else roi_align_fwd_generic<0><<<grid, 256, 0, st>>>(feat, rois, out, total, C, H, W, PH, PW, scale, fs, os);
+    const Strides fs = feat_strides(feat_layout, C, H, W), os = out_strides(out_layout, C, PH, PW);
+    const long long total = (long long)R * C * PH * PW;
+    const AlignFwdPlan pl = plan_roi_align_fwd(feat_layout, B, C, H, W, R, PH, PW, avg, out_layout, g_i2v_tuning);
+    const dim3 grid(pl.grid), thr(pl.threads);
+    switch (pl.form * 2 + pl.avg) {
+    case AF_ROI128 * 2 + 1: roi_align_fwd_roi_kernel<1><<<grid, thr, 0, st>>>(feat, rois, out, R, C, H, W, PH, PW, scale); break;
+    case AF_ROI128 * 2 + 0: roi_align_fwd_roi_kernel<0><<<grid, thr, 0, st>>>(feat, rois, out, R, C, H, W, PH, PW, scale); break;
+    case AF_ROI64 * 2 + 1: roi_align_fwd_roi_kernel<1, 64><<<grid, thr, 0, st>>>(feat, rois, out, R, C, H, W, PH, PW, scale); break;
+    case AF_ROI64 * 2 + 0: roi_align_fwd_roi_kernel<0, 64><<<grid, thr, 0, st>>>(feat, rois, out, R, C, H, W, PH, PW, scale); break;
+    case AF_COLS * 2 + 1: roi_align_fwd_nhwc_cols<1><<<grid, thr, 0, st>>>(feat, rois, out, R, C, H, W, PH, PW, scale, os); break;
+    case AF_COLS * 2 + 0: roi_align_fwd_nhwc_cols<0><<<grid, thr, 0, st>>>(feat, rois, out, R, C, H, W, PH, PW, scale, os); break;
+    case AF_ROWS * 2 + 1: roi_align_fwd_nhwc<1><<<grid, thr, 0, st>>>(feat, rois, out, C, H, W, PH, PW, scale, os); break;
+    case AF_ROWS * 2 + 0: roi_align_fwd_nhwc<0><<<grid, thr, 0, st>>>(feat, rois, out, C, H, W, PH, PW, scale, os); break;
+    case AF_GENERIC * 2 + 1: roi_align_fwd_generic<1><<<grid, thr, 0, st>>>(feat, rois, out, total, C, H, W, PH, PW, scale, fs, os); break;
+    case AF_GENERIC * 2 + 0: roi_align_fwd_generic<0><<<grid, thr, 0, st>>>(feat, rois, out, total, C, H, W, PH, PW, scale, fs, os); break;
     }
     I2V_CHECK_LAUNCH("roi_align_fwd");
+    return I2V_OK;
+}
+
+// The plan of i2v_roi_align_fwd as numbers (include/i2vsgg_hip.h has the field order).
+extern "C" int32_t i2v_roi_align_fwd_plan(int32_t feat_layout, int32_t B, int32_t C, int32_t H, int32_t W, int32_t R, int32_t PH,
+                                          int32_t PW, int32_t avg, int32_t out_layout, int32_t* out, int32_t n_out) {
+    I2V_CHECK_ARG(out && n_out >= I2V_ROI_ALIGN_FWD_PLAN_FIELDS, "roi_align_fwd_plan: out needs room for I2V_ROI_ALIGN_FWD_PLAN_FIELDS values");
+    I2V_CHECK_ARG(B > 0 && C > 0 && H >= 2 && W >= 2 && R >= 0 && PH > 0 && PW > 0, "roi_align_fwd_plan: bad shape");
+    I2V_CHECK_ARG(avg == 0 || avg == 1, "roi_align_fwd_plan: avg must be 0/1");
+    const AlignFwdPlan pl = plan_roi_align_fwd(feat_layout, B, C, H, W, R, PH, PW, avg, out_layout, g_i2v_tuning);
+    const int32_t v[I2V_ROI_ALIGN_FWD_PLAN_FIELDS] = {pl.status, pl.form, pl.avg, (int32_t)pl.grid, pl.threads, (int32_t)pl.lds};
+    std::copy(v, v + I2V_ROI_ALIGN_FWD_PLAN_FIELDS, out);
     return I2V_OK;
 }
 
@@ -1176,9 +1181,13 @@ extern "C" int32_t i2v_roi_align_bwd(const float* gout, int32_t out_layout, cons
     I2V_CHECK_ARG(B > 0 && C > 0 && H >= 2 && W >= 2 && R >= 0 && PH > 0 && PW > 0, "roi_align_bwd: bad shape");
     I2V_CHECK_ARG(avg == 0 || avg == 1, "roi_align_bwd: avg must be 0/1");
     hipStream_t st = (hipStream_t)stream;
-    Strides os = out_strides(out_layout, C, PH, PW), fs = feat_strides(feat_layout, C, H, W);
-    if (avg) roi_align_bwd_kernel<1><<<R * (PH + 1), 256, 0, st>>>(gout, rois, gfeat, C, H, W, PH, PW, scale, fs, os);
-    else roi_align_bwd_kernel<0><<<R * PH, 256, 0, st>>>(gout, rois, gfeat, C, H, W, PH, PW, scale, fs, os);
+    const Strides os = out_strides(out_layout, C, PH, PW), fs = feat_strides(feat_layout, C, H, W);
+    const AlignBwdPlan pl = plan_roi_align_bwd_scatter(R, PH, avg);
+    const dim3 grid(pl.grid), thr(pl.threads);
+    switch (pl.avg) {
+    case 1: roi_align_bwd_kernel<1><<<grid, thr, 0, st>>>(gout, rois, gfeat, C, H, W, PH, PW, scale, fs, os); break;
+    case 0: roi_align_bwd_kernel<0><<<grid, thr, 0, st>>>(gout, rois, gfeat, C, H, W, PH, PW, scale, fs, os); break;
+    }
     I2V_CHECK_LAUNCH("roi_align_bwd");
     return I2V_OK;
 }
@@ -1188,6 +1197,18 @@ extern "C" size_t i2v_roi_align_bwd_gather_workspace_bytes(int32_t R, int32_t C,
     return 0;                           // round 5: one kernel, nothing staged in global memory (the entry stays for its callers)
 }
 
+namespace {
+struct RabArgs { const float* gout; const float* rois; int R, PH, PW; float scale; float* gfeat; int B, C, H, W; };
+
+// one gather launch: the kernel's opt-in to kRabLdsMax of dynamic LDS, then the plan's grid
+template <auto Kernel>
+int32_t launch_gather(const char* name, const AlignBwdPlan& pl, const RabArgs& a, hipStream_t st) {
+    I2V_ALLOW_LDS(name, kRabLdsMax, Kernel);
+    Kernel<<<dim3(pl.grid), dim3(pl.threads), pl.lds, st>>>(a.gout, a.rois, a.gfeat, a.R, a.PH, a.PW, a.scale, a.B, a.C, a.H, a.W);
+    return I2V_OK;
+}
+}  // namespace
+
 extern "C" int32_t i2v_roi_align_bwd_gather(const float* gout, const float* rois, int32_t R, int32_t PH, int32_t PW, float scale,
                                             int32_t avg, float* gfeat, int32_t B, int32_t C, int32_t H, int32_t W, void* ws,
                                             size_t ws_bytes, void* stream) {
@@ -1195,41 +1216,38 @@ extern "C" int32_t i2v_roi_align_bwd_gather(const float* gout, const float* rois
     I2V_CHECK_ARG(gout && rois && gfeat, "roi_align_bwd_gather: null pointer");
     I2V_CHECK_ARG(B > 0 && C > 0 && H >= 2 && W >= 2 && R > 0 && PH > 0 && PW > 0, "roi_align_bwd_gather: bad shape");
     I2V_CHECK_ARG(avg == 0 || avg == 1, "roi_align_bwd_gather: avg must be 0/1");
-    I2V_CHECK_ARG(C % 128 == 0, "roi_align_bwd_gather: C must be a multiple of 128 (NHWC in and out)");
-    const size_t AH = PH + avg, AW = PW + avg;
-    I2V_CHECK_ARG(AW <= RAB_MAXA, "roi_align_bwd_gather: at most 8 sample columns (pooled_w + avg <= 8)");
-    const bool form2 = g_i2v_tuning[I2V_TUNE_ROIALIGN_BWD] != 0;        // round 6: waves that never meet (0: round 5's staged batches)
-    const size_t lds = (size_t)(W + 2) * 128 * sizeof(float) + (form2 ? 0 : (size_t)RAB_BATCH * RAB_MAXA * 128 * sizeof(float)) + RAB_SEG * sizeof(unsigned short);
-    I2V_CHECK_ARG(lds <= 60 * 1024 && (long long)R * AH < (1ll << 29), "roi_align_bwd_gather: map too wide for the LDS row buffer");
-    I2V_CHECK_ARG((long long)B * H * (C / 128) < (1ll << 31), "roi_align_bwd_gather: grid too large");
-    I2V_CHECK_ARG((long long)R * PH * PW * C * 4 < (1ll << 31), "roi_align_bwd_gather: grad_out beyond the 2 GiB a 32-bit buffer offset reaches");
+    const AlignBwdPlan pl = plan_roi_align_bwd_gather(R, PH, PW, avg, B, C, H, W, g_i2v_tuning, i2v::NUM_CU);
+    I2V_CHECK_ARG(pl.status == PLAN_OK, "%s", refusal_text(pl.status));
     hipStream_t st = (hipStream_t)stream;
-    // the second form with one pair group per workgroup (128 channels) or two (64 channels, half the dependent chain): two where
-    // the launch fits the chip at once (its time is then its longest list's), one where it runs in rounds (the sum counts)
-    const bool two = form2 && (long long)B * H * (C / 64) <= 4ll * 256;       // four workgroups on each of the 256 CUs
-    static bool once = [] {
-        (void)hipFuncSetAttribute((const void*)roi_align_bwd_row_kernel<0, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, 60 * 1024);
-        (void)hipFuncSetAttribute((const void*)roi_align_bwd_row_kernel<1, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, 60 * 1024);
-        (void)hipFuncSetAttribute((const void*)roi_align_bwd_row_kernel<1, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 60 * 1024);
-        (void)hipFuncSetAttribute((const void*)roi_align_bwd_row2_kernel<0, 0, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 60 * 1024);
-        (void)hipFuncSetAttribute((const void*)roi_align_bwd_row2_kernel<1, 0, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 60 * 1024);
-        (void)hipFuncSetAttribute((const void*)roi_align_bwd_row2_kernel<1, 1, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 60 * 1024);
-        (void)hipFuncSetAttribute((const void*)roi_align_bwd_row2_kernel<0, 0, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 60 * 1024);
-        (void)hipFuncSetAttribute((const void*)roi_align_bwd_row2_kernel<1, 0, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 60 * 1024);
-        (void)hipFuncSetAttribute((const void*)roi_align_bwd_row2_kernel<1, 1, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 60 * 1024);
-        return true;
-    }();
-    (void)once;
-    const dim3 grid(B * H * (C / 128)), grid2(B * H * (C / 64));
-    const int p7 = avg && PH == 7 && PW == 7;
-#define RAB2(A, P, G, GRID) roi_align_bwd_row2_kernel<A, P, G><<<GRID, 256, lds, st>>>(gout, rois, gfeat, R, PH, PW, scale, B, C, H, W)
-    if (form2 && two) { if (p7) RAB2(1, 1, 2, grid2); else if (avg) RAB2(1, 0, 2, grid2); else RAB2(0, 0, 2, grid2); }
-    else if (form2) { if (p7) RAB2(1, 1, 1, grid); else if (avg) RAB2(1, 0, 1, grid); else RAB2(0, 0, 1, grid); }
-#undef RAB2
-    else if (avg && PH == 7 && PW == 7) roi_align_bwd_row_kernel<1, 1><<<grid, 256, lds, st>>>(gout, rois, gfeat, R, PH, PW, scale, B, C, H, W);
-    else if (avg) roi_align_bwd_row_kernel<1, 0><<<grid, 256, lds, st>>>(gout, rois, gfeat, R, PH, PW, scale, B, C, H, W);
-    else roi_align_bwd_row_kernel<0, 0><<<grid, 256, lds, st>>>(gout, rois, gfeat, R, PH, PW, scale, B, C, H, W);
+    const RabArgs a = {gout, rois, R, PH, PW, scale, gfeat, B, C, H, W};
+    int32_t rc = I2V_OK;
+    switch (((pl.form * 4 + pl.groups) * 2 + pl.avg) * 2 + pl.p7) {         // (form, groups, avg, p7)
+    case ((AB_GATHER_ROW2 * 4 + 2) * 2 + 1) * 2 + 1: rc = launch_gather<roi_align_bwd_row2_kernel<1, 1, 2>>("roi_align_bwd_row2_kernel", pl, a, st); break;
+    case ((AB_GATHER_ROW2 * 4 + 2) * 2 + 1) * 2 + 0: rc = launch_gather<roi_align_bwd_row2_kernel<1, 0, 2>>("roi_align_bwd_row2_kernel", pl, a, st); break;
+    case ((AB_GATHER_ROW2 * 4 + 2) * 2 + 0) * 2 + 0: rc = launch_gather<roi_align_bwd_row2_kernel<0, 0, 2>>("roi_align_bwd_row2_kernel", pl, a, st); break;
+    case ((AB_GATHER_ROW2 * 4 + 1) * 2 + 1) * 2 + 1: rc = launch_gather<roi_align_bwd_row2_kernel<1, 1, 1>>("roi_align_bwd_row2_kernel", pl, a, st); break;
+    case ((AB_GATHER_ROW2 * 4 + 1) * 2 + 1) * 2 + 0: rc = launch_gather<roi_align_bwd_row2_kernel<1, 0, 1>>("roi_align_bwd_row2_kernel", pl, a, st); break;
+    case ((AB_GATHER_ROW2 * 4 + 1) * 2 + 0) * 2 + 0: rc = launch_gather<roi_align_bwd_row2_kernel<0, 0, 1>>("roi_align_bwd_row2_kernel", pl, a, st); break;
+    case ((AB_GATHER_ROW * 4 + 0) * 2 + 1) * 2 + 1: rc = launch_gather<roi_align_bwd_row_kernel<1, 1>>("roi_align_bwd_row_kernel", pl, a, st); break;
+    case ((AB_GATHER_ROW * 4 + 0) * 2 + 1) * 2 + 0: rc = launch_gather<roi_align_bwd_row_kernel<1, 0>>("roi_align_bwd_row_kernel", pl, a, st); break;
+    case ((AB_GATHER_ROW * 4 + 0) * 2 + 0) * 2 + 0: rc = launch_gather<roi_align_bwd_row_kernel<0, 0>>("roi_align_bwd_row_kernel", pl, a, st); break;
+    }
+    if (rc) return rc;
     I2V_CHECK_LAUNCH("roi_align_bwd_gather");
+    return I2V_OK;
+}
+
+// The route and the plan of a RoIAlign backward as numbers (include/i2vsgg_hip.h has the field order); the arguments of
+// i2v_roi_align_bwd.  A GATHER route is i2v_roi_align_bwd_gather's launch, a SCATTER route i2v_roi_align_bwd's.
+extern "C" int32_t i2v_roi_align_bwd_plan(int32_t out_layout, int32_t R, int32_t PH, int32_t PW, int32_t avg, int32_t feat_layout,
+                                          int32_t B, int32_t C, int32_t H, int32_t W, int32_t* out, int32_t n_out) {
+    I2V_CHECK_ARG(out && n_out >= I2V_ROI_ALIGN_BWD_PLAN_FIELDS, "roi_align_bwd_plan: out needs room for I2V_ROI_ALIGN_BWD_PLAN_FIELDS values");
+    I2V_CHECK_ARG(B > 0 && C > 0 && H >= 2 && W >= 2 && R >= 0 && PH > 0 && PW > 0, "roi_align_bwd_plan: bad shape");
+    I2V_CHECK_ARG(avg == 0 || avg == 1, "roi_align_bwd_plan: avg must be 0/1");
+    const AlignBwdPlan pl = plan_roi_align_bwd(out_layout, R, PH, PW, avg, feat_layout, B, C, H, W, g_i2v_tuning, i2v::NUM_CU);
+    const int32_t v[I2V_ROI_ALIGN_BWD_PLAN_FIELDS] = {pl.status, pl.route, pl.form, pl.groups, pl.avg, pl.p7, (int32_t)pl.grid,
+                                                      pl.threads, (int32_t)pl.lds};
+    std::copy(v, v + I2V_ROI_ALIGN_BWD_PLAN_FIELDS, out);
     return I2V_OK;
 }
 

@@ -7,9 +7,11 @@
 // -ffp-contract=off) so IoU threshold decisions match the reference's CPU path bit
 // for bit on the same boxes.
 #include "common.h"
+#include "roi_plan.h"
 #include <algorithm>
 
 namespace {
+using namespace roiplan;
 
 // ------------------------------------------------------------------ decode + clip
 // One thread per anchor (b, y, x, a); NHWC inputs make (y,x,a) the memory order of both
@@ -173,7 +175,7 @@ __global__ void gather_dets(const unsigned long long* __restrict__ keys, int P, 
 __device__ inline float hw_max(float a, float b) { float r; asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
 __device__ inline float hw_min(float a, float b) { float r; asm("v_min_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
 
-constexpr int NMS_MASK_WAVES = 1;        // row blocks (waves) per workgroup sharing one column block's boxes: measured 1 / 2 / 4 waves 47.2 / 47.6 / 52.5 us at N = 12000 (18.0 / 19.4 / 18.4 at 6000)
+// NMS_MASK_WAVES (row blocks per workgroup), SCAN_THREADS, SCAN_PIPE_WORDS, SUPER_ROWS, SUPER_WORDS, NMS_SWEEPS: roi_plan.h
 
 __global__ void __launch_bounds__(64 * NMS_MASK_WAVES)
 nms_mask_kernel(const float* __restrict__ dets, int n, int nblk, float thresh,
@@ -260,7 +262,6 @@ nms_mask_kernel(const float* __restrict__ dets, int n, int nblk, float thresh,
 //     all 16 waves then OR the mask rows of the rows just kept into the LDS "removed"
 //     bitmap.  Stops after max_keep kept rows.  Replaces the host scan of
 //     nms_cuda_kernel.cu:132-144 and the Python while-loop of nms_cpu.py:18-32.
-constexpr int SCAN_THREADS = 1024;
 constexpr int SCAN_MAX_BLK = 1024;      // n <= 65536
 
 __global__ void __launch_bounds__(SCAN_THREADS)
@@ -319,11 +320,10 @@ nms_scan_kernel(const unsigned long long* __restrict__ mask, int n, int nblk, in
 // barrier per block, then none: LDS counters polled both ways): bit-exact on every golden case and SLOWER -- 264 us with one
 // barrier, 370-420 us polling, against 186 us for the form below (N = 12000 clustered; DESIGN.md 5.10 has the stamps).  Neither
 // the barrier count nor a drained prefetch (LDS-only barriers: 185 us) is what a block's ~2k cycles are made of.
-// Pipelined variant for n <= 12288 (every RPN case): the mask rows of block rb+1 are fetched into
+// Pipelined variant for n <= 12352 (every RPN case): the mask rows of block rb+1 are fetched into
 // registers (4 rows per wave x 3 words per lane) while block rb is being resolved and folded in, so
 // global-load latency is off the serial chain; the chain per 64-row block is the 64-step resolve in
 // wave 0 plus two workgroup barriers.
-constexpr int SCAN_PIPE_WORDS = 3;      // words per lane: covers nblk - 1 <= 192 columns
 
 // a value every lane holds alike (read from LDS: the compiler must assume otherwise), moved to scalar registers
 __device__ inline unsigned long long uniform64(unsigned long long v) {
@@ -459,7 +459,6 @@ nms_scan_pipelined_kernel(const unsigned long long* __restrict__ mask, int n, in
 //   faster than the pipelined kernel (181.8 against 185.2 us): what the scan costs is the resolve's ~190 cycles of dependent
 //   scalar instructions per KEPT row, not the barriers, the fetch or the fold.
 // Either way the greedy keep set, row by row: bit-exact.
-constexpr int SUPER_ROWS = 1024, SUPER_WORDS = 16, NMS_SWEEPS = 48;
 
 __global__ void __launch_bounds__(SCAN_THREADS)
 nms_scan_super_kernel(const unsigned long long* __restrict__ mask, int n, int nblk, int max_keep,
@@ -752,23 +751,21 @@ ProposalWs carve(void* ws, int B, long long n_all, int n_top) {
     return w;
 }
 
-int launch_nms(const float* dets, int n_img, int n, float thresh, int max_keep, int* keep, int* num,
-               unsigned long long* mask, hipStream_t st) {
-    const int nblk = (n + 63) / 64;
-    nms_mask_kernel<<<dim3(nblk, i2v_cdiv(nblk, NMS_MASK_WAVES), n_img), 64 * NMS_MASK_WAVES, 0, st>>>(dets, n, nblk, thresh, mask);
-    static bool once = [] {
-        (void)hipFuncSetAttribute((const void*)nms_scan_super_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, SUPER_ROWS * SUPER_WORDS * 8);
-        return true;
-    }();
-    (void)once;
-    if (nblk - 1 <= 64 * SCAN_PIPE_WORDS && g_i2v_tuning[I2V_TUNE_NMS_SCAN] && (long long)n * nblk * 8 < (1ll << 31))
-        nms_scan_super_kernel<<<n_img, SCAN_THREADS, SUPER_ROWS * SUPER_WORDS * 8, st>>>(mask, n, nblk, max_keep, keep, num,
-                                                                                         g_i2v_tuning[I2V_TUNE_NMS_SCAN] < 2 ? 0 : g_i2v_tuning[I2V_TUNE_NMS_SCAN] == 2 ? NMS_SWEEPS : g_i2v_tuning[I2V_TUNE_NMS_SCAN]);
-    else if (nblk - 1 <= 64 * SCAN_PIPE_WORDS)
-        nms_scan_pipelined_kernel<<<n_img, SCAN_THREADS, 0, st>>>(mask, n, nblk, max_keep, keep, num);
-    else
-        nms_scan_kernel<<<n_img, SCAN_THREADS, 0, st>>>(mask, n, nblk, max_keep, keep, num);
-    return 0;
+// mask, then the greedy scan; which scan is plan_nms's decision (roi_plan.h)
+int32_t launch_nms(const float* dets, int n_img, int n, float thresh, int max_keep, int* keep, int* num,
+                   unsigned long long* mask, hipStream_t st) {
+    const NmsPlan pl = plan_nms(n_img, n, g_i2v_tuning);
+    const dim3 mgrid(pl.mask_grid[0], pl.mask_grid[1], pl.mask_grid[2]), grid(pl.grid), thr(pl.threads);
+    nms_mask_kernel<<<mgrid, dim3(pl.mask_threads), 0, st>>>(dets, n, pl.nblk, thresh, mask);
+    switch (pl.form) {
+    case NS_SUPER:
+        I2V_ALLOW_LDS("nms_scan_super_kernel", pl.lds, nms_scan_super_kernel);
+        nms_scan_super_kernel<<<grid, thr, pl.lds, st>>>(mask, n, pl.nblk, max_keep, keep, num, pl.sweeps);
+        break;
+    case NS_PIPELINED: nms_scan_pipelined_kernel<<<grid, thr, 0, st>>>(mask, n, pl.nblk, max_keep, keep, num); break;
+    case NS_GENERIC: nms_scan_kernel<<<grid, thr, 0, st>>>(mask, n, pl.nblk, max_keep, keep, num); break;
+    }
+    return I2V_OK;
 }
 
 
@@ -926,8 +923,21 @@ extern "C" int32_t i2v_nms_sorted(const float* dets, int32_t n_img, int32_t n, f
         i2v_set_error("nms_sorted: workspace %zu < %zu", ws_bytes, i2v_nms_workspace_bytes(n_img, n));
         return I2V_ERR_WORKSPACE;
     }
-    launch_nms(dets, n_img, n, thresh, max_keep, keep_out, num_out, (unsigned long long*)ws, st);
+    const int32_t rc = launch_nms(dets, n_img, n, thresh, max_keep, keep_out, num_out, (unsigned long long*)ws, st);
+    if (rc) return rc;
     I2V_CHECK_LAUNCH("nms_sorted");
+    return I2V_OK;
+}
+
+// The plan of launch_nms as numbers (include/i2vsgg_hip.h has the field order): the launches i2v_nms_sorted,
+// i2v_rpn_proposal (n = its pre-NMS top-n) and i2v_det_postprocess make for n boxes of n_img images.
+extern "C" int32_t i2v_nms_plan(int32_t n_img, int32_t n, int32_t* out, int32_t n_out) {
+    I2V_CHECK_ARG(out && n_out >= I2V_NMS_PLAN_FIELDS, "nms_plan: out needs room for I2V_NMS_PLAN_FIELDS values");
+    I2V_CHECK_ARG(n_img > 0 && n > 0 && n <= 64 * SCAN_MAX_BLK, "nms_plan: bad shape");
+    const NmsPlan pl = plan_nms(n_img, n, g_i2v_tuning);
+    const int32_t v[I2V_NMS_PLAN_FIELDS] = {pl.status, pl.nblk, (int32_t)pl.mask_grid[0], (int32_t)pl.mask_grid[1], (int32_t)pl.mask_grid[2],
+                                            pl.mask_threads, pl.form, pl.sweeps, (int32_t)pl.grid, pl.threads, (int32_t)pl.lds};
+    std::copy(v, v + I2V_NMS_PLAN_FIELDS, out);
     return I2V_OK;
 }
 
@@ -993,7 +1003,8 @@ extern "C" int32_t i2v_rpn_proposal(const float* cls, int32_t is_prob, const flo
     const int P = launch_sort(w.score, B, (int)n_all, w.keys, st);
     gather_dets<<<dim3(i2v_cdiv(n_top, 256), B), 256, 0, st>>>(w.keys, P, w.prop, w.score, (int)n_all, n_top,
                                                                w.dets, w.src);
-    launch_nms(w.dets, B, n_top, thresh, post, w.keep, w.num, w.mask, st);
+    const int32_t rc = launch_nms(w.dets, B, n_top, thresh, post, w.keep, w.num, w.mask, st);
+    if (rc) return rc;
     write_rois<<<dim3(i2v_cdiv(post, 256), B), 256, 0, st>>>(w.dets, w.src, w.keep, w.num, n_top, post, rois,
                                                              kept_idx, num_kept);
     I2V_CHECK_LAUNCH("rpn_proposal");

@@ -59,6 +59,18 @@ ROIALIGN_BWD_KERNELS = {"roi_align_bwd_row2_kernel": 1}     # (I2V_TUNE_ROIALIGN
 NMS_KERNELS = {"nms_mask_kernel": 1, "nms_scan_super_kernel": 1}      # (I2V_TUNE_NMS_SCAN = 0: nms_scan_pipelined_kernel, round 5's scan)
 
 
+ROUTE_SCATTER, ROUTE_GATHER = 0, 1
+_ROI_ALIGN_BWD_PLAN = ("status", "route", "form", "groups", "avg", "p7", "grid", "threads", "lds")
+
+
+def roi_align_bwd_plan(out_nchw, R, ph, pw, avg, nhwc, B, C, H, W):
+    """The route and launch the library plans for this backward (csrc/roi_plan.h; fields: include/i2vsgg_hip.h)."""
+    out = (ctypes.c_int32 * len(_ROI_ALIGN_BWD_PLAN))()
+    check(lib.i2v_roi_align_bwd_plan(LAYOUT_NCHW if out_nchw else LAYOUT_NHWC, R, ph, pw, int(avg), LAYOUT_NHWC if nhwc else LAYOUT_NCHW,
+                                     B, C, H, W, out, len(out)), "roi_align_bwd_plan")
+    return dict(zip(_ROI_ALIGN_BWD_PLAN, out))
+
+
 class _RoIAlignFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, feat, rois, ph, pw, scale, avg, out_nchw):
@@ -84,9 +96,11 @@ class _RoIAlignFn(torch.autograd.Function):
         shape, nhwc, ph, pw, scale, avg, out_nchw = ctx.meta
         B, C, H, W = shape
         gout = gout.contiguous() if out_nchw else gout.contiguous(memory_format=_CL)
-        if ROIALIGN_BWD_GATHER and nhwc and not out_nchw and C % 128 == 0 and W * 512 + 21504 <= 60 * 1024 and pw + avg <= 8 and rois.size(0) > 0:
+        plan = roi_align_bwd_plan(out_nchw, rois.size(0), ph, pw, avg, nhwc, B, C, H, W)
+        if ROIALIGN_BWD_GATHER and plan["route"] == ROUTE_GATHER:
             # the gather form: every element of the gradient map written once, in the reference's serial order (deterministic,
-            # no atomics, no zero-fill, no workspace: one kernel since round 5)
+            # no atomics, no zero-fill, no workspace: one kernel since round 5).  A shape the route takes and the entry point
+            # refuses (plan["status"]) raises there; it does not scatter
             gfeat = torch.empty(shape, device=gout.device, dtype=torch.float32, memory_format=_CL)
             check(lib.i2v_roi_align_bwd_gather(ptr(gout), ptr(rois), rois.size(0), ph, pw, scale, avg, ptr(gfeat), B, C, H, W,
                                                None, 0, stream()), "roi_align_bwd_gather")

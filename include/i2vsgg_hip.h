@@ -590,6 +590,39 @@ int32_t i2v_conv_fwd_plan(int32_t B, int32_t H, int32_t W, int32_t Cin, int32_t 
 int32_t i2v_conv_wgrad_plan(int32_t B, int32_t H, int32_t W, int32_t Cin, int32_t Cout, int32_t KH, int32_t KW,
                             int32_t stride, int32_t pad, int32_t nbatch, int32_t beta_nonzero, int32_t fused,
                             int32_t has_row_scale, int32_t ext_part_cap, size_t ws_bytes, int32_t* out, int32_t n_out);
+/* The launch plans of RoIAlign and NMS (csrc/roi_plan.h computes them; the launches follow them), in the same style:
+ * pure functions of the shape and the tuning table, fields as int32 into out[0 .. n_out), 0 or < 0 for a bad argument (too
+ * few slots included); a shape the entry point refuses is a plan with out[0] != 0 (the entry's I2V_ERR_ARG).
+ * i2v_roi_align_fwd_plan: the arguments of i2v_roi_align_fwd.  Fields:
+ *    0 status        always 0
+ *    1 form          0 ROI128, 1 ROI64 (roi_align_fwd_roi_kernel: one ROI x 128 / 64 channels per workgroup), 2 COLS
+ *                    (roi_align_fwd_nhwc_cols), 3 ROWS (roi_align_fwd_nhwc), 4 GENERIC (roi_align_fwd_generic)
+ *    2 avg           the kernel's <AVG>        3 grid        4 threads        5 dynamic LDS bytes
+ * i2v_roi_align_bwd_plan: the arguments of i2v_roi_align_bwd.  Fields:
+ *    0 status        0 ok; the gather entry's refusals: 1 C % 128, 2 more than 8 sample columns, 3 map too wide for the LDS row
+ *                    buffer, 4 R * (pooled_h + avg) >= 2^29, 5 grid too large, 6 grad_out of 2 GiB or more
+ *    1 route         0 SCATTER (i2v_roi_align_bwd), 1 GATHER (i2v_roi_align_bwd_gather): NHWC in and out, C % 128 == 0, W <= 78,
+ *                    pooled_w + avg <= 8, R > 0.  A status on a GATHER route is that entry's error, not a reason to scatter
+ *    2 form          0 SCATTER (roi_align_bwd_kernel), 1 GATHER_ROW (roi_align_bwd_row_kernel, I2V_TUNE_ROIALIGN_BWD = 0),
+ *                    2 GATHER_ROW2 (roi_align_bwd_row2_kernel)
+ *    3 groups        GATHER_ROW2: pair groups per workgroup, 2 iff B * H * (C / 64) <= 4 x the CU count, else 1; other forms 0
+ *    4 avg  5 p7     the kernel's <AVG, P7> (p7: the 7 x 7 average grid)      6 grid      7 threads      8 dynamic LDS bytes
+ * i2v_nms_plan: the mask launch and the scan of i2v_nms_sorted / i2v_rpn_proposal / i2v_det_postprocess for n boxes of each
+ * of n_img images.  Fields:
+ *    0 status        always 0                 1 nblk  64-box blocks
+ *    2..4 mask grid x, y, z                   5 mask threads
+ *    6 form          0 SUPER (nms_scan_super_kernel), 1 PIPELINED (nms_scan_pipelined_kernel), 2 GENERIC (nms_scan_kernel:
+ *                    nblk - 1 > 192, that is n > 12352)
+ *    7 sweeps        SUPER: fixed-point sweeps before the serial resolve (I2V_TUNE_NMS_SCAN: 1 -> 0, 2 -> 48, v > 2 -> v)
+ *    8 grid          9 threads       10 dynamic LDS bytes */
+#define I2V_ROI_ALIGN_FWD_PLAN_FIELDS 6
+#define I2V_ROI_ALIGN_BWD_PLAN_FIELDS 9
+#define I2V_NMS_PLAN_FIELDS           11
+int32_t i2v_roi_align_fwd_plan(int32_t feat_layout, int32_t B, int32_t C, int32_t H, int32_t W, int32_t R, int32_t pooled_h,
+                               int32_t pooled_w, int32_t avg, int32_t out_layout, int32_t* out, int32_t n_out);
+int32_t i2v_roi_align_bwd_plan(int32_t out_layout, int32_t R, int32_t pooled_h, int32_t pooled_w, int32_t avg, int32_t feat_layout,
+                               int32_t B, int32_t C, int32_t H, int32_t W, int32_t* out, int32_t n_out);
+int32_t i2v_nms_plan(int32_t n_img, int32_t n, int32_t* out, int32_t n_out);
 /* Tuning knobs (process-wide, host side only; the library reads no environment variable).  key = I2V_TUNE_*. */
 #define I2V_TUNE_CONV_SPEC            0   /* retired (rounds 1-5: the 8-wave loader / MFMA specialisation of conv_igemm_f32): only <= 0 is accepted */
 #define I2V_TUNE_SPLIT_TARGET         1   /* workgroups per CU a split-K launch aims for (default 2) */
@@ -616,7 +649,7 @@ int32_t i2v_conv_wgrad_plan(int32_t B, int32_t H, int32_t W, int32_t Cin, int32_
 #define I2V_TUNE_GEMM_DMA            22   /* how the pointwise / plain-GEMM kernel stages its operand tiles (round 6).  0: global -> registers -> ds_write_b128 (rounds 2-5).  1: LDS-DMA (buffer_load ... lds, the column swizzle on the source address), 32-k stages, same LDS image.  2: LDS-DMA with 16-k stages (64-byte LDS rows): half the LDS per workgroup, twice the barriers.  Bit-equal results in all three */
 #define I2V_TUNE_WGRAD_DMA           23   /* staging of the second-generation filter-gradient kernel on pointwise / linear problems (round 6).  0: global -> registers -> transposing ds_write_b128.  1: LDS-DMA into the [pixel][column] image, the group swizzle on the source column.  Bit-equal */
 #define I2V_TUNE_ROIALIGN_BWD        24   /* the gather form of the RoIAlign backward (round 6).  1: a wave owns 32 channels of the row buffer, a lane = (sample column, 4 channels), gradients from grad_out to registers, 16-byte read-add-writes.  0: round 5's form (lane = channel x cell parity, gradients and tap records staged in LDS per batch of four pairs) */
-#define I2V_TUNE_NMS_SCAN            25   /* the greedy scan of NMS for up to 12288 boxes (round 6).  2 (default): super-blocks of 1024 rows whose triangle of the mask sits in LDS, resolved by fixed-point sweeps (keep <- alive & ~OR of the kept rows' words, from keep = alive: exact at its fixed point, a few sweeps), a serial resolve for a super-block that has not settled after 48 sweeps; a value v > 2: the same with v sweeps at most.  1: the super-blocks with the serial resolve only.  0: round 5's scan (64-row blocks, two barriers each).  The same keep lists in every mode */
+#define I2V_TUNE_NMS_SCAN            25   /* the greedy scan of NMS for up to 12352 boxes (nblk - 1 <= 192: i2v_nms_plan; more take the generic scan in every mode) (round 6).  2 (default): super-blocks of 1024 rows whose triangle of the mask sits in LDS, resolved by fixed-point sweeps (keep <- alive & ~OR of the kept rows' words, from keep = alive: exact at its fixed point, a few sweeps), a serial resolve for a super-block that has not settled after 48 sweeps; a value v > 2: the same with v sweeps at most.  1: the super-blocks with the serial resolve only.  0: round 5's scan (64-row blocks, two barriers each).  The same keep lists in every mode */
 #define I2V_TUNE_FC_UPDATE           26   /* the fused filter-gradient + SGD-momentum update of linear / pointwise layers of <= 256 rows (i2v_conv_wgrad_sgd; round 7).  1 (default): the persistent streaming kernel (one workgroup per CU owns 128 filters -- their gradient rows held in registers -- and a contiguous range of 64-tap tiles, the tap ranges pinned to XCDs, filter / momentum tiles loaded two tiles ahead).  0: the tiled fused kernel of rounds 3-6.  Bit-equal */
 #define I2V_TUNE_COUNT               27
 /* Keys CONV_SPEC (> 0), STAGGER, FC_FOLD, GEMM_X3, GEMM_PERSIST, WGRAD_PRIO belonged to kernel variants that were measured and lost

@@ -214,6 +214,37 @@ def test_roi_align_bwd_gather_is_deterministic_and_equals_the_scatter(ops, oracl
     assert float(g1.abs().sum()) > 0
 
 
+@pytest.mark.parametrize("W", [78, 79])
+@pytest.mark.parametrize("avg", [True, False])
+def test_roi_align_bwd_on_both_sides_of_the_gather_route(ops, oracle, W, avg):
+    """The widest map the backward's route hands to the gather (W = 78, csrc/roi_plan.h kRabRouteMaxW) and the first that
+    scatters (W = 79), which no other shape here reaches: each against the C oracle with its neighbours' bounds -- the gather
+    to 2e-6 of the largest gradient and twice for the same bits, the atomic scatter to rtol = atol = 2e-5."""
+    from i2vsgg_amd import ops as O
+    cops, _ = oracle
+    B, C, H = 1, 128, 6
+    rng = np.random.default_rng(W + int(avg))
+    rois = _rois_cases(rng, B, H, W)
+    plan = O.roi_align_bwd_plan(False, rois.shape[0], 7, 7, avg, True, B, C, H, W)
+    assert plan["status"] == 0 and plan["route"] == (O.ROUTE_GATHER if W == 78 else O.ROUTE_SCATTER) and O.ROIALIGN_BWD_GATHER
+    gout = rng.standard_normal((rois.shape[0], C, 7, 7), dtype=np.float32)
+    ref = (cops.roi_align_avg_bwd if avg else cops.roi_align_bwd)(gout, rois, (B, C, H, W), 1.0 / 16.0)
+    rt, gt = torch.from_numpy(rois).to(DEV), torch.from_numpy(gout).to(DEV).contiguous(memory_format=torch.channels_last)
+
+    def run():
+        feat = torch.zeros((B, C, H, W), device=DEV).contiguous(memory_format=torch.channels_last).requires_grad_()
+        O.roi_align(feat, rt, 7, 7, 1.0 / 16.0, avg=avg).backward(gt)
+        return feat.grad
+
+    g1 = run()
+    assert float(g1.abs().sum()) > 0
+    if W == 78:
+        assert torch.equal(g1, run())                                    # no atomics: the same bits every time
+        np.testing.assert_allclose(g1.cpu().numpy(), ref, rtol=0, atol=2e-6 * float(np.abs(ref).max()))
+    else:
+        np.testing.assert_allclose(g1.cpu().numpy(), ref, rtol=2e-5, atol=2e-5)
+
+
 @pytest.mark.parametrize("C,H,W,B", [(4, 9, 11, 2), (6, 9, 11, 2), (64, 19, 32, 2), (1024, 38, 63, 1)])
 @pytest.mark.parametrize("sampling", [0, 2])
 def test_roi_align_sampled_fwd_bwd(ops, oracle, C, H, W, B, sampling):

@@ -45,6 +45,17 @@ def test_ladder_table_is_complete():
     assert nc.NMS_SWEEPS == 48 and nc.SUPER_ROWS == 1024
     # 12352 rows are the last n the super-block scan takes (nblk - 1 <= 192), 12353 the first of the generic scan
     assert (12352 + 63) // 64 - 1 == 192 and (12353 + 63) // 64 - 1 == 193
+    # ... and so says the library's own plan (csrc/roi_plan.h through i2v_nms_plan; fields: include/i2vsgg_hip.h)
+    import ctypes
+    from i2vsgg_amd import build
+    build.build()
+    from i2vsgg_amd._lib import lib
+    out = (ctypes.c_int32 * 11)()
+    forms = []
+    for n in (12352, 12353):
+        assert lib.i2v_nms_plan(1, n, out, 11) == 0 and out[0] == 0 and out[1] == (n + 63) // 64
+        forms.append((out[6], out[7]))
+    assert forms == [(0, nc.NMS_SWEEPS), (2, 0)]             # SUPER with the default sweeps, then GENERIC
 
 
 @pytest.mark.parametrize("name", sorted(LADDER_T))
