@@ -8,6 +8,7 @@
 // Layout (i2vsgg_amd/detection_eval.py pack()): detections lie in results-file order -- class, then image, then row --
 // so class c owns [cls_off[c], cls_off[c+1]) and a (class, image) pair with detections is one contiguous segment.
 #include "table_common.h"
+#include "sort.h"
 
 #define DE_MAXG 4096         // ground truths of one (class, image): 64 lanes x 64 claimed bits in registers
 #define DE_TP 1
@@ -43,15 +44,7 @@ det_eval_match_kernel(const int* __restrict__ seg_det_off, const int* __restrict
         return;
     }
     // 1. rank by (key descending, position ascending); any number of detections, 64 at a time
-    for (int i = lane; i < nd; i += 64) {
-        const int k = det_key[d0 + i];
-        int r = 0;
-        for (int j = 0; j < nd; ++j) {
-            const int kj = det_key[d0 + j];
-            r += (kj > k || (kj == k && j < i)) ? 1 : 0;
-        }
-        order[d0 + r] = i;
-    }
+    for (int i = lane; i < nd; i += 64) order[d0 + i2v_rank_desc(det_key + d0, nd, i)] = i;
     __syncthreads();                                     // one wave: makes ``order`` visible to all its lanes
     // 2. walk them; lane l owns ground truths l, l + 64, ... and bit k of ``claimed`` is ground truth l + 64k
     unsigned long long claimed = 0;
@@ -131,10 +124,7 @@ extern "C" int32_t i2v_det_eval_match(const int32_t* seg_det_off, const int32_t*
 // ---------------------------------------------------------------------------------------------------------------------
 // Sort key, ASCENDING: class (8 bits) | 0xFFFFFFFF - (key as order-preserving u32) (32 bits) | position in class (24 bits):
 // classes stay where they are, within a class the key descends and equal keys keep their results-file order.  Padding
-// is all ones and sorts last.
-constexpr int DE_SORT_TILE = 4096;      // u64 keys per LDS tile (32 KiB of the 160 KiB: occupancy is not bound by it)
-constexpr int DE_SORT_THREADS = 512;
-
+// is all ones and sorts last.  The sort itself is the library's (sort.hip), one segment.
 __global__ void __launch_bounds__(256)
 det_eval_keys_kernel(const int* __restrict__ det_key, const int* __restrict__ cls_off, int n_cls, int n_det, int P,
                      unsigned long long* __restrict__ out, int* status) {
@@ -156,44 +146,6 @@ det_eval_keys_kernel(const int* __restrict__ det_key, const int* __restrict__ cl
         }
     }
     out[i] = k;
-}
-
-__global__ void __launch_bounds__(DE_SORT_THREADS)
-det_eval_sort_local(unsigned long long* __restrict__ data, int k_lo, int k_hi) {
-    __shared__ unsigned long long s[DE_SORT_TILE];
-    const long long base = (long long)blockIdx.x * DE_SORT_TILE;
-    for (int i = threadIdx.x; i < DE_SORT_TILE; i += DE_SORT_THREADS) s[i] = data[base + i];
-    __syncthreads();
-    const long long gbase = base;
-    for (long long k = k_lo; k <= k_hi; k <<= 1) {
-        int j0 = (k >> 1) < DE_SORT_TILE ? (int)(k >> 1) : (DE_SORT_TILE >> 1);
-        for (int j = j0; j > 0; j >>= 1) {
-            for (int t = threadIdx.x; t < DE_SORT_TILE / 2; t += DE_SORT_THREADS) {
-                const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1));
-                const bool asc = (((gbase + i) & k) == 0);
-                const unsigned long long a = s[i], b = s[i | j];
-                if ((a > b) == asc) { s[i] = b; s[i | j] = a; }
-            }
-            __syncthreads();
-        }
-    }
-    for (int i = threadIdx.x; i < DE_SORT_TILE; i += DE_SORT_THREADS) data[base + i] = s[i];
-}
-
-__global__ void __launch_bounds__(256)
-det_eval_sort_global(unsigned long long* __restrict__ data, int P, int k, int j) {
-    const int t = blockIdx.x * 256 + threadIdx.x;
-    if (t >= P / 2) return;
-    const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1));
-    const bool asc = ((i & k) == 0);
-    const unsigned long long a = data[i], b = data[i | j];
-    if ((a > b) == asc) { data[i] = b; data[i | j] = a; }
-}
-
-static inline int de_padded(int n) {
-    int p = DE_SORT_TILE;
-    while (p < n) p <<= 1;
-    return p;
 }
 
 // inclusive scans over the 1024 threads of a workgroup, in thread order; ``red`` holds one entry per wave
@@ -341,7 +293,7 @@ det_eval_curve_kernel(const unsigned long long* __restrict__ keys, const int* __
 extern "C" size_t i2v_det_eval_curve_workspace_bytes(int32_t n_det) {
     if (n_det <= 0) return I2V_STATUS_BYTES;
     // status, keys, envelope
-    return I2V_STATUS_BYTES + i2v_align((size_t)de_padded(n_det) * 8) + i2v_align((size_t)n_det * sizeof(double));
+    return I2V_STATUS_BYTES + i2v_align((size_t)sort_padded(n_det) * 8) + i2v_align((size_t)n_det * sizeof(double));
 }
 
 extern "C" int32_t i2v_det_eval_curve(const int32_t* det_key, const int32_t* cls_off, const int32_t* flag, const int32_t* npos,
@@ -362,16 +314,10 @@ extern "C" int32_t i2v_det_eval_curve(const int32_t* det_key, const int32_t* cls
     unsigned long long* keys = (unsigned long long*)((char*)ws + I2V_STATUS_BYTES);
     double* env = nullptr;
     if (n_det > 0) {
-        const int P = de_padded(n_det);
+        const int P = sort_padded(n_det);
         env = (double*)((char*)ws + I2V_STATUS_BYTES + i2v_align((size_t)P * 8));
         det_eval_keys_kernel<<<i2v_cdiv(P, 256), 256, 0, st>>>(det_key, cls_off, n_cls, n_det, P, keys, status);
-        const int tiles = P / DE_SORT_TILE;
-        det_eval_sort_local<<<tiles, DE_SORT_THREADS, 0, st>>>(keys, 2, DE_SORT_TILE);
-        for (long long k = (long long)DE_SORT_TILE * 2; k <= P; k <<= 1) {
-            for (long long j = k >> 1; j >= DE_SORT_TILE; j >>= 1)
-                det_eval_sort_global<<<i2v_cdiv(P / 2, 256), 256, 0, st>>>(keys, P, (int)k, (int)j);
-            det_eval_sort_local<<<tiles, DE_SORT_THREADS, 0, st>>>(keys, (int)k, (int)k);
-        }
+        i2v_launch_sort_u64(keys, 1, P, st);
     }
     det_eval_curve_kernel<<<n_cls, DE_CURVE_THREADS, 0, st>>>(keys, cls_off, flag, npos, n_det, perm, cum_tp, cum_fp, rec, prec,
                                                               env, ap_area, ap_11pt, status);

@@ -1,4 +1,4 @@
-// The launch plans of RoIAlign forward / backward in csrc/roi_ops.hip and of launch_nms in csrc/rpn.hip:
+// The launch plans of RoIAlign forward / backward in csrc/roi_ops.hip and of launch_nms in csrc/nms.hip:
 // which kernel form, template selectors, grid, threads and dynamic LDS a shape takes.  The counterpart of conv_plan.h --
 // host-only and pure: no HIP, no globals; the tuning table (g_i2v_tuning, indexed by I2V_TUNE_*) and the CU count come in as
 // arguments, so the host tests check every decision without a GPU (tests/test_roi_plan_host.py against

@@ -1,5 +1,5 @@
 // What the packed-table ops share (seqnms, video, det_eval, recognition, relation_features, relation_targets,
-// image_relations): the workspace's status header, the tests of an offset table's entries and the +1 overlap.  The rules the
+// image_relations): the workspace's status header, the tests of an offset table's entries, the +1 overlap and the counting rank.  The rules the
 // device and host forms keep bit for bit are stated here once; the host side is i2vsgg_amd/packing.py.
 #pragma once
 #include "common.h"
@@ -36,4 +36,17 @@ __device__ __forceinline__ double i2v_overlap_plus1(const double* a, const doubl
     const double aa = ((a[2] - a[0]) + 1.0) * ((a[3] - a[1]) + 1.0);
     const double ab = ((b[2] - b[0]) + 1.0) * ((b[3] - b[1]) + 1.0);
     return inter / ((aa + ab) - inter);
+}
+
+// position of key[i] in a stable descending order of key[0 .. n): keys larger than it, and equal keys in front of it.  Counted,
+// so for short tables only (a frame's predictions, a segment's detections); the keys lie in LDS or in global memory.
+template <typename T>
+__device__ __forceinline__ int i2v_rank_desc(const T* key, int n, int i) {
+    const T k = key[i];
+    int r = 0;
+    for (int j = 0; j < n; ++j) {
+        const T kj = key[j];
+        r += (kj > k || (kj == k && j < i)) ? 1 : 0;
+    }
+    return r;
 }

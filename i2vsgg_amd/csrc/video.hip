@@ -15,17 +15,6 @@
 // Association
 // ---------------------------------------------------------------------------------------------------------------------
 
-// rank of key[i] in descending order, equal keys in index order (a stable sort's position); n <= 100, keys in LDS
-__device__ __forceinline__ int va_rank_desc(const double* key, int n, int i) {
-    const double k = key[i];
-    int r = 0;
-    for (int j = 0; j < n; ++j) {
-        const double kj = key[j];
-        r += (kj > k || (kj == k && j < i)) ? 1 : 0;
-    }
-    return r;
-}
-
 // lib/utils.py:20-32 in its own operation order (no +1; empty or touching intersection: 0): not i2v_overlap_plus1's arithmetic
 __device__ __forceinline__ double va_iou(const double* a, const double* b) {
     const double left = a[0] > b[0] ? a[0] : b[0];
@@ -91,7 +80,7 @@ video_associate_kernel(const int* __restrict__ frame_off, const int* __restrict_
         if (t < n) s_key[t] = score[p0 + t];
         __syncthreads();
         if (t < n) {
-            const int r = va_rank_desc(s_key, n, t);
+            const int r = i2v_rank_desc(s_key, n, t);
             C.score[r] = s_key[t];
             C.src[r] = t;
             for (int k = 0; k < 3; ++k) C.trip[r][k] = trip[(size_t)(p0 + t) * 3 + k];
@@ -101,7 +90,7 @@ video_associate_kernel(const int* __restrict__ frame_off, const int* __restrict_
         // 2. the open relations by their current mean, descending, stable in the order the last frame touched them
         if (t < m) s_key[t] = P.sum[t] / (double)P.cnt[t];
         __syncthreads();
-        if (t < m) s_order[va_rank_desc(s_key, m, t)] = t;
+        if (t < m) s_order[i2v_rank_desc(s_key, m, t)] = t;
         __syncthreads();
         // 3. compatibility of every prediction with every candidate: equal triplet, both boxes IoU >= 0.5
         {
@@ -258,7 +247,7 @@ video_associate_tracks_kernel(const int* __restrict__ frame_off, const int* __re
         if (t < n) s_key[t] = score[p0 + t];
         __syncthreads();
         if (t < n) {
-            const int r = va_rank_desc(s_key, n, t);
+            const int r = i2v_rank_desc(s_key, n, t);
             c_score[r] = s_key[t];
             c_src[r] = t;
             for (int k = 0; k < 3; ++k) c_key[r][k] = key[(size_t)(p0 + t) * 3 + k];
@@ -535,12 +524,7 @@ video_match_kernel(const int* __restrict__ pred_off, const double* __restrict__ 
     }
     for (int i = lane; i < np; i += 64) s_score[i] = pred_score[p0 + i];
     __syncthreads();
-    for (int i = lane; i < np; i += 64) {
-        const double k = s_score[i];
-        int r = 0;
-        for (int j = 0; j < np; ++j) r += (s_score[j] > k || (s_score[j] == k && j < i)) ? 1 : 0;
-        s_order[r] = i;
-    }
+    for (int i = lane; i < np; i += 64) s_order[i2v_rank_desc(s_score, np, i)] = i;
     __syncthreads();
     unsigned long long det = 0;                          // bit k: ground truth lane + 64k is detected
     for (int q = 0; q < np; ++q) {

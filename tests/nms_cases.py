@@ -1,4 +1,4 @@
-"""Built cases of greedy NMS (i2v_nms_sorted: nms_mask_kernel and the three scan kernels of csrc/rpn.hip), shared by the host test
+"""Built cases of greedy NMS (i2v_nms_sorted: nms_mask_kernel and the three scan kernels of csrc/nms.hip), shared by the host test
 and the GPU test, plus the two host helpers the cases are designed with.  Which regime a case lands in -- how many fixed-point
 sweeps a 1024-row super-block needs, whether a pair lies inside the mask kernel's band around the threshold -- is decided here and
 asserted on the CPU (tests/test_nms_cases_host.py); the GPU test only compares keep lists.  Everything is seeded numpy; nothing

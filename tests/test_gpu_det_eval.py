@@ -1,5 +1,6 @@
 """The detection-evaluation kernels (csrc/det_eval.hip) against the reference's voc_eval (tests/golden/det_eval.npz) and,
-on a larger seeded set with heavy score ties, against the host form of i2vsgg_amd.detection_eval bit for bit."""
+on a larger seeded set with heavy score ties and on small ones around the sort's 4096-key tile, against the host form of
+i2vsgg_amd.detection_eval bit for bit."""
 import copy
 
 import numpy as np
@@ -70,6 +71,29 @@ def test_kernels_equal_the_host_form_on_a_large_set_with_ties(fresh):
     for name in ("rec", "prec", "ap_area", "ap_11pt"):
         assert _same_doubles(cur[name], hcur[name]), name
     assert np.isnan(cur["ap_area"]).sum() == 1 and (cur["ap_area"][~np.isnan(cur["ap_area"])] > 0).sum() >= 13
+
+
+@pytest.mark.parametrize("n_cls", [1, 2])
+@pytest.mark.parametrize("n_det", [1, 4095, 4096, 4097, 8193])
+def test_curve_equals_the_host_form_around_the_sort_tile(n_det, n_cls):
+    """det_eval_curve between the golden set and the large one: one key short of a 4096-key sort tile, exactly one, one
+    more (two tiles, the first global step) and three tiles' worth (four, one of them all padding), as one class and as
+    two classes whose boundary lies inside a tile; at most 7 distinct scores, so the order rests on the positions."""
+    from i2vsgg_amd import detection_eval as de, ops
+    rng = np.random.RandomState(1000 * n_cls + n_det)
+    det_key = rng.choice(np.array([-2000, -1, 0, 1, 499, 500, 999], np.int32), n_det)
+    assert len(np.unique(det_key)) <= 7
+    cls_off = np.array([0, n_det] if n_cls == 1 else [0, n_det // 3, n_det], np.int32)
+    flag = rng.choice(np.array([de.IGNORED, de.TP, de.FP], np.int32), n_det)
+    npos = np.array([max(1, n_det // 2), max(1, n_det // 4)][:n_cls], np.int32)
+    pk = de.Packed(n_classes=n_cls, det_key=det_key, cls_off=cls_off, npos=npos)
+    hcur = de.curve_arrays_host(pk, flag)
+    names = ("perm", "cum_tp", "cum_fp", "rec", "prec", "ap_area", "ap_11pt")
+    cur = dict((n, t.cpu().numpy()) for n, t in zip(names, ops.det_eval_curve(det_key, cls_off, flag, npos, device=DEV)))
+    for name in ("perm", "cum_tp", "cum_fp"):
+        assert np.array_equal(cur[name], hcur[name]), name
+    for name in ("rec", "prec", "ap_area", "ap_11pt"):
+        assert np.array_equal(_bits(cur[name]), _bits(hcur[name])), name
 
 
 def test_two_runs_give_the_same_bits(fresh):

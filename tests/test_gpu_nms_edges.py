@@ -1,4 +1,4 @@
-"""Greedy NMS on the device (i2v_nms_sorted: nms_mask_kernel and the scan kernels of csrc/rpn.hip) on the built edge cases of
+"""Greedy NMS on the device (i2v_nms_sorted: nms_mask_kernel and the scan kernels of csrc/nms.hip) on the built edge cases of
 tests/nms_cases.py, against the oracle's nms_sorted, bit for bit: deep suppress-release chains around the sweep cap of the
 fixed-point resolve, across the 1024-row super-block edge and at the hand-over to the generic scan; pairs whose IoU is the
 threshold, one ulp to either side, and around the mask kernel's band; degenerate boxes.  Which regime each case lands in is

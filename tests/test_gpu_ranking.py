@@ -1,5 +1,5 @@
-"""The ranking kernels of csrc/rpn.hip (i2v_sort_desc and what is built on it: i2v_rpn_proposal, i2v_det_postprocess[_info],
-i2v_relation_topk) on ties, saturated scores, signed zeros, non-finite keys and at the edges of the 4096-key sort tile.
+"""The ranking kernels (i2v_sort_desc of csrc/sort.hip and what is built on it: i2v_rpn_proposal of csrc/rpn.hip,
+i2v_det_postprocess[_info] and i2v_relation_topk of csrc/det_post.hip) on ties, saturated scores, signed zeros, non-finite keys and at the edges of the 4096-key sort tile.
 Every comparison is exact: integer orders, bit-equal boxes and scores against the CPU oracles.  Keys are NaN-free (the NaN
 order of i2v_sort_desc is unspecified).  Needs a real MI355X: `pytest -m gpu`."""
 import numpy as np
