@@ -375,6 +375,70 @@ def gen_rpn_layers(cfg):
     save("proposal_target", "placeholders", **out)
 
 
+def gen_target_edges(cfg):
+    """tests/golden/target_edges.npz: the reference's own bbox_overlaps_batch, bbox_transform_batch, _AnchorTargetLayer and
+    _ProposalTargetLayer on the built cases of tests/target_cases.py.  Outputs only -- the inputs are rebuilt from the builders.
+    Kept small: overlap matrices for the edge cases, max / argmax alone for the shape grid (shared boxes, one image); anchor
+    targets only where the outside weight is non-zero (the labelled anchors: what the loss reads); labels as int8.  A scene the
+    reference raises on is kept out and the exception's text recorded under ``<key>_error``."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import target_cases as tc
+    from model.rpn import bbox_transform as bt
+    from model.rpn.anchor_target_layer import _AnchorTargetLayer
+    from model.rpn.proposal_target_layer_cascade import _ProposalTargetLayer
+    t = torch.from_numpy
+    out = {}
+
+    def overlaps(case):
+        return bt.bbox_overlaps_batch(t(case.boxes), t(case.gt)).numpy()
+    for case in tc.edge_overlap_cases():
+        ov = overlaps(case)
+        mx, am = torch.max(t(ov), 2)
+        out.update({"ov_%s_ov" % case.name: ov, "ov_%s_max" % case.name: mx.numpy(), "ov_%s_argmax" % case.name: am.numpy().astype(np.int16)})
+    for N in tc.SHAPE_N:
+        for K in tc.SHAPE_K:
+            case = tc.shape_case(1, N, K, "shared")
+            mx, am = torch.max(t(overlaps(case)), 2)
+            out.update({"sh_%s_max" % case.name: mx.numpy(), "sh_%s_argmax" % case.name: am.numpy().astype(np.int16)})
+    for case in tc.transform_cases():
+        out["tf_%s_targets" % case.name] = bt.bbox_transform_batch(t(case.ex), t(case.gt)).numpy()
+
+    atl = _AnchorTargetLayer(16, cfg.ANCHOR_SCALES, cfg.ANCHOR_RATIOS)
+    for sc in tc.anchor_scenes():
+        B, (H, W) = sc.gt.shape[0], sc.feat
+        nb = (sc.gt[:, :, 2] > 0).sum(1).astype(np.int64)
+        np.random.seed(3)
+        try:
+            L, T, IW, OW = (x.numpy() for x in atl((torch.zeros(B, 18, H, W), t(sc.gt), t(sc.im_info), t(nb))))
+        except Exception as e:                                            # noqa: BLE001 -- whatever the reference raises
+            out["at_%s_error" % sc.name] = np.array("%s: %s" % (type(e).__name__, e))
+            print("    anchor scene %s: the reference raises %s: %s" % (sc.name, type(e).__name__, e))
+            continue
+        assert np.array_equal(L, L.astype(np.int8)) and np.array_equal(IW, (IW > 0).astype(np.float32))
+        out.update({"at_%s_labels" % sc.name: L.astype(np.int8), "at_%s_inw" % sc.name: (IW > 0), "at_%s_outw" % sc.name: OW,
+                    "at_%s_targets_labelled" % sc.name: T[OW > 0]})
+
+    ptl = _ProposalTargetLayer(16)
+    saved = (cfg.TRAIN.BG_THRESH_LO, cfg.TRAIN.BATCH_SIZE)
+    for sc in tc.proposal_scenes():
+        nb = (sc.gt[:, :, 2] > 0).sum(1).astype(np.int64)
+        for lo in tc.BG_LO:
+            for R in tc.PROPOSAL_R:
+                cfg.TRAIN.BG_THRESH_LO, cfg.TRAIN.BATCH_SIZE = lo, R
+                key = "pt_%s_lo%02d_R%d" % (sc.name, int(lo * 10), R)
+                np.random.seed(3)
+                try:
+                    res = ptl(t(sc.rois), t(sc.gt), t(nb))
+                except Exception as e:                                    # noqa: BLE001
+                    out[key + "_error"] = np.array("%s: %s" % (type(e).__name__, e))
+                    print("    proposal scene %s: the reference raises %s: %s" % (key, type(e).__name__, e))
+                    continue
+                for name, x in zip(("rois", "labels", "targets", "inw", "outw"), res):
+                    out["%s_%s" % (key, name)] = x.numpy()
+    cfg.TRAIN.BG_THRESH_LO, cfg.TRAIN.BATCH_SIZE = saved
+    save("target_edges", "placeholders", **out)
+
+
 def _load(module, params, prefix):
     sd = {k[len(prefix):]: v for k, v in params.items() if k.startswith(prefix)}
     missing = module.load_state_dict(sd, strict=False)
@@ -1388,7 +1452,7 @@ def main():
     os.makedirs(GOLD, exist_ok=True)
     todo = a.only.split(",") if a.only else ["direct", "roialign", "roialign_fresh", "tails", "rpn", "nets", "full", "ctx", "step",
                                              "vrd", "video", "det_eval", "recognition", "video_relation_feat", "track_eval",
-                                             "video_nms"]
+                                             "video_nms", "target_edges"]
     if "direct" in todo:
         print("[direct imports]")
         gen_direct()
@@ -1425,11 +1489,13 @@ def main():
     if "video_nms" in todo:
         print("[video relation NMS: viou of lib/utils.py compiled from its own lines, the greedy loop taken from its table]")
         gen_video_nms()
-    if any(t in todo for t in ("rpn", "nets", "full", "vrd", "ctx", "step")):
+    if any(t in todo for t in ("rpn", "nets", "full", "vrd", "ctx", "step", "target_edges")):
         print("[imports with placeholders]")
         cfg = install_placeholders()
         if "rpn" in todo:
             gen_rpn_layers(cfg)
+        if "target_edges" in todo:
+            gen_target_edges(cfg)
         if "nets" in todo:
             gen_nets(cfg)
         if "full" in todo:
