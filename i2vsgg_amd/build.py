@@ -6,7 +6,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libi2vsgg_hip.so")
-SOURCES = ["api.cpp", "roi_ops.hip", "rpn.hip", "sort.hip", "nms.hip", "det_post.hip", "conv.hip", "wgrad.hip", "elementwise.hip", "heads.hip",
+SOURCES = ["api.cpp", "roi_ops.hip", "rpn.hip", "sort.hip", "nms.hip", "soft_nms.hip", "det_post.hip", "conv.hip", "wgrad.hip", "elementwise.hip", "heads.hip",
            "image.hip", "winograd.hip", "dstyle.hip", "video.hip", "video_nms.hip", "det_eval.hip", "seqnms.hip", "track_stitch.hip", "recognition.hip", "relation_targets.hip",
            "image_relations.hip", "relation_features.hip", "proposal_eval.hip"]
 # -ffp-contract=off: box / IoU / ROIAlign arithmetic must round once per operation like the

@@ -13,7 +13,7 @@ void i2v_set_error(const char* fmt, ...) {
     va_end(ap);
 }
 
-extern "C" int32_t i2v_version(void) { return 110; }   // 0.1.10: + i2v_video_relation_nms
+extern "C" int32_t i2v_version(void) { return 111; }   // 0.1.11: + i2v_soft_nms, i2v_det_postprocess_soft[_info]
 extern "C" const char* i2v_last_error(void) { return g_err; }
 
 // Tuning table (i2v_set_tuning): the library reads no environment variable; a host that wants the knobs sets them

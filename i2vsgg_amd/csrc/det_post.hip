@@ -1,11 +1,13 @@
 // What the test loops do with a frame's network outputs: the detector's eval post-processing (decode, per class
 // threshold / sort / NMS, the image-wide cut) and the relation triplet ranking.  Both rank through i2v_sort_desc (sort.hip);
-// the detections go through i2v_nms_sorted (nms.hip).
+// the detections go through i2v_nms_sorted (nms.hip) or, in the *_soft entries, through launch_soft_nms (soft_nms.hip).
 //
 // Box arithmetic is fp32 with one rounding per operation (built with
 // -ffp-contract=off) so IoU threshold decisions match the reference's CPU path bit
 // for bit on the same boxes.
 #include "common.h"
+#include "roi_plan.h"
+#include "soft_nms.h"
 #include <algorithm>
 
 namespace {
@@ -170,14 +172,24 @@ extern "C" size_t i2v_det_postprocess_workspace_bytes(int32_t R, int32_t C) {
     return det_carve(nullptr, R, C).bytes;
 }
 
+// the *_soft entries' extra arguments; nullptr: the greedy NMS
+struct DetSoft { int method; float sigma, min_score; };
+
 static int32_t det_postprocess(const float* rois, const float* cls_prob, const float* bbox_pred,
                                int32_t class_agnostic, const float* stds, const float* means, float im_h,
                                float im_w, float im_scale, const float* info, int32_t R, int32_t C, float score_thresh,
-                               float nms_thresh, int32_t max_per_image, float* dets, int32_t* counts, void* ws,
-                               size_t ws_bytes, void* stream) {
+                               float nms_thresh, int32_t max_per_image, const DetSoft* soft, float* dets, int32_t* counts,
+                               void* ws, size_t ws_bytes, void* stream) {
     I2V_CHECK_ARG(rois && cls_prob && bbox_pred && dets && counts, "det_postprocess: null pointer");
     I2V_CHECK_ARG(R > 0 && C > 1 && (info || im_scale > 0.f), "det_postprocess: bad shape");
     I2V_CHECK_ARG((stds == nullptr) == (means == nullptr), "det_postprocess: stds and means go together");
+    if (soft) {              // what launch_soft_nms would refuse, before anything is launched
+        I2V_CHECK_ARG(soft->method == I2V_SOFT_NMS_HARD || soft->method == I2V_SOFT_NMS_LINEAR || soft->method == I2V_SOFT_NMS_GAUSSIAN,
+                      "det_postprocess_soft: method must be I2V_SOFT_NMS_HARD, _LINEAR or _GAUSSIAN");
+        I2V_CHECK_ARG(soft->method != I2V_SOFT_NMS_GAUSSIAN || soft->sigma > 0.f, "det_postprocess_soft: sigma must be positive");
+        const int status = roiplan::plan_soft_nms(C - 1, R).status;
+        I2V_CHECK_ARG(status == roiplan::PLAN_OK, "%s", roiplan::soft_nms_refusal_text(status));
+    }
     if (!ws || ws_bytes < i2v_det_postprocess_workspace_bytes(R, C)) {
         i2v_set_error("det_postprocess: workspace too small");
         return I2V_ERR_WORKSPACE;
@@ -195,9 +207,16 @@ static int32_t det_postprocess(const float* rois, const float* cls_prob, const f
     int rc = i2v_sort_desc(w.keys, C - 1, R, w.order, w.sort_ws, w.sort_ws_bytes, stream);
     if (rc) return rc;
     det_gather_kernel<<<i2v_cdiv(n, 256), 256, 0, st>>>(w.boxes, w.keys, w.order, w.n_valid, R, C, w.dets);
-    rc = i2v_nms_sorted(w.dets, C - 1, R, nms_thresh, 0, w.keep, w.num, w.nms_ws, w.nms_ws_bytes, stream);
-    if (rc) return rc;
-    det_compact_kernel<<<C - 1, 256, 0, st>>>(w.dets, w.keep, w.num, w.n_valid, R, w.tmp, w.all_scores, w.cnt, w.total);
+    if (soft) {
+        // the same tmp / all_scores / cnt / total as the two launches below leave; keep holds the source rows, unused
+        rc = launch_soft_nms(w.dets, w.n_valid, C - 1, R, soft->method, nms_thresh, soft->sigma, soft->min_score, w.tmp, w.keep,
+                             w.cnt, w.all_scores, w.total, st);
+        if (rc) return rc;
+    } else {
+        rc = i2v_nms_sorted(w.dets, C - 1, R, nms_thresh, 0, w.keep, w.num, w.nms_ws, w.nms_ws_bytes, stream);
+        if (rc) return rc;
+        det_compact_kernel<<<C - 1, 256, 0, st>>>(w.dets, w.keep, w.num, w.n_valid, R, w.tmp, w.all_scores, w.cnt, w.total);
+    }
     if (max_per_image > 0) {
         rc = i2v_sort_desc(w.all_scores, 1, n, w.order2, w.sort_ws, w.sort_ws_bytes, stream);
         if (rc) return rc;
@@ -213,7 +232,7 @@ extern "C" int32_t i2v_det_postprocess(const float* rois, const float* cls_prob,
                                        float nms_thresh, int32_t max_per_image, float* dets, int32_t* counts, void* ws,
                                        size_t ws_bytes, void* stream) {
     return det_postprocess(rois, cls_prob, bbox_pred, class_agnostic, stds, means, im_h, im_w, im_scale, nullptr, R, C,
-                           score_thresh, nms_thresh, max_per_image, dets, counts, ws, ws_bytes, stream);
+                           score_thresh, nms_thresh, max_per_image, nullptr, dets, counts, ws, ws_bytes, stream);
 }
 
 extern "C" int32_t i2v_det_postprocess_info(const float* rois, const float* cls_prob, const float* bbox_pred,
@@ -223,7 +242,30 @@ extern "C" int32_t i2v_det_postprocess_info(const float* rois, const float* cls_
                                             void* ws, size_t ws_bytes, void* stream) {
     I2V_CHECK_ARG(im_info, "det_postprocess_info: null im_info");
     return det_postprocess(rois, cls_prob, bbox_pred, class_agnostic, stds, means, 0.f, 0.f, 0.f, im_info, R, C,
-                           score_thresh, nms_thresh, max_per_image, dets, counts, ws, ws_bytes, stream);
+                           score_thresh, nms_thresh, max_per_image, nullptr, dets, counts, ws, ws_bytes, stream);
+}
+
+extern "C" int32_t i2v_det_postprocess_soft(const float* rois, const float* cls_prob, const float* bbox_pred,
+                                            int32_t class_agnostic, const float* stds, const float* means, float im_h,
+                                            float im_w, float im_scale, int32_t R, int32_t C, float score_thresh,
+                                            float nms_thresh, int32_t max_per_image, int32_t method, float sigma,
+                                            float min_score, float* dets, int32_t* counts, void* ws, size_t ws_bytes,
+                                            void* stream) {
+    const DetSoft soft = {method, sigma, min_score};
+    return det_postprocess(rois, cls_prob, bbox_pred, class_agnostic, stds, means, im_h, im_w, im_scale, nullptr, R, C,
+                           score_thresh, nms_thresh, max_per_image, &soft, dets, counts, ws, ws_bytes, stream);
+}
+
+extern "C" int32_t i2v_det_postprocess_soft_info(const float* rois, const float* cls_prob, const float* bbox_pred,
+                                                 int32_t class_agnostic, const float* stds, const float* means,
+                                                 const float* im_info, int32_t R, int32_t C, float score_thresh,
+                                                 float nms_thresh, int32_t max_per_image, int32_t method, float sigma,
+                                                 float min_score, float* dets, int32_t* counts, void* ws, size_t ws_bytes,
+                                                 void* stream) {
+    I2V_CHECK_ARG(im_info, "det_postprocess_soft_info: null im_info");
+    const DetSoft soft = {method, sigma, min_score};
+    return det_postprocess(rois, cls_prob, bbox_pred, class_agnostic, stds, means, 0.f, 0.f, 0.f, im_info, R, C,
+                           score_thresh, nms_thresh, max_per_image, &soft, dets, counts, ws, ws_bytes, stream);
 }
 
 extern "C" size_t i2v_relation_topk_workspace_bytes(int32_t n_pairs, int32_t n_rel) {

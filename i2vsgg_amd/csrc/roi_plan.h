@@ -1,4 +1,5 @@
-// The launch plans of RoIAlign forward / backward in csrc/roi_ops.hip and of launch_nms in csrc/nms.hip:
+// The launch plans of RoIAlign forward / backward in csrc/roi_ops.hip, of launch_nms in csrc/nms.hip and of launch_soft_nms in
+// csrc/soft_nms.hip (tests/test_soft_nms_host.py holds its cases):
 // which kernel form, template selectors, grid, threads and dynamic LDS a shape takes.  The counterpart of conv_plan.h --
 // host-only and pure: no HIP, no globals; the tuning table (g_i2v_tuning, indexed by I2V_TUNE_*) and the CU count come in as
 // arguments, so the host tests check every decision without a GPU (tests/test_roi_plan_host.py against
@@ -196,6 +197,45 @@ inline NmsPlan plan_nms(int n_img, int n, const int* tuning) {
     } else {
         q.form = in_registers ? NS_PIPELINED : NS_GENERIC;
     }
+    return q;
+}
+
+// ---------------------------------------------------------------- Soft-NMS (one set per workgroup, rows on chip)
+constexpr int SOFT_NMS_MAX_N = 4096;     // rows of a set: 16 waves x 64 lanes x 4 rows in registers, their boxes in 64 KiB of LDS
+constexpr int SOFT_NMS_WAVE_MAX_N = 512; // up to here one wave holds the set (8 rows per lane) and never meets a barrier
+constexpr int SOFT_NMS_BLOCK_WAVES = 16;
+
+enum SoftNmsStatus { SOFT_NMS_ROWS = 1 };        // more than SOFT_NMS_MAX_N rows per set
+enum SoftNmsForm { SN_WAVE = 0, SN_BLOCK = 1 };
+
+inline const char* soft_nms_refusal_text(int status) {
+    return status == SOFT_NMS_ROWS ? "soft_nms: at most 4096 rows per set" : "";
+}
+
+struct SoftNmsPlan {
+    int status;
+    int form;                // SoftNmsForm
+    int waves;               // 1 (WAVE) or SOFT_NMS_BLOCK_WAVES
+    int rows;                // rows per lane <K>: row k * threads + thread sits in register k
+    unsigned grid;           // one workgroup per set
+    int threads;
+    size_t lds;              // dynamic LDS: a float4 per row, BLOCK: and two rounds of one 64-bit key per wave
+};
+
+inline SoftNmsPlan plan_soft_nms(int n_set, int n) {
+    SoftNmsPlan q = {};
+    if (n > SOFT_NMS_MAX_N) {
+        q.status = SOFT_NMS_ROWS;
+        return q;
+    }
+    q.form = n <= SOFT_NMS_WAVE_MAX_N ? SN_WAVE : SN_BLOCK;
+    q.waves = q.form == SN_WAVE ? 1 : SOFT_NMS_BLOCK_WAVES;
+    q.threads = 64 * q.waves;
+    const int need = (int)cdiv(n, q.threads);
+    // the instantiated register counts: 1, 2, 4, 5 (300 rows, the test loop's own size, in one wave), 8
+    q.rows = need <= 2 ? (need < 1 ? 1 : need) : need <= 4 ? 4 : need == 5 ? 5 : 8;
+    q.grid = (unsigned)n_set;
+    q.lds = (size_t)n * 16 + (q.form == SN_BLOCK ? (size_t)2 * q.waves * 8 : 0);
     return q;
 }
 

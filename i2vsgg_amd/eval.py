@@ -24,6 +24,7 @@ import torch
 from . import launch, ops
 from .graphs import GraphRecorder, replay_graph
 from .model.utils.config import cfg
+from .soft_nms import options as soft_nms_options
 from .staging import _Slot, _place_u8, parse_u8_meta, place_frames, step_uploader
 
 _FEATURE_SINK = [None]
@@ -171,12 +172,16 @@ class DetectStep(_FrameGraphStep):
     the detections', and ``collect()`` returns ``(results, proposals)``: next to today's list, per frame the (n, 4) float32
     proposals in scaled-image coordinates, best first, without the zero rows the proposal layer pads with
     (``trim_proposals``).  With the default ``False`` no buffer, copy or graph node is added and ``collect()`` returns what it
-    returns today."""
+    returns today.
+
+    ``soft_nms``: None or "off" (the greedy NMS), a method name, a (method, sigma, min_score) triple or a ``soft_nms.SoftNMS``:
+    Soft-NMS per class in the captured post-processing (``ops.detection_postprocess(soft_nms=...)``, ``Nt = cfg.TEST.NMS``)."""
 
     def __init__(self, net, frames=2, thresh=0.0, max_per_image=100, class_agnostic=False, device="cuda:0", use_graph=True,
-                 max_graphs=8, keep_proposals=False):
+                 max_graphs=8, keep_proposals=False, soft_nms=None):
         super().__init__(net, frames, device, use_graph, max_graphs)
         self.thresh, self.max_per_image, self.class_agnostic = float(thresh), int(max_per_image), bool(class_agnostic)
+        self.soft_nms = soft_nms_options(soft_nms)
         self.R, self.C = int(cfg.TEST.RPN_POST_NMS_TOP_N), int(net.n_classes)
         self.info = torch.zeros((self.frames, 3), device=self.dev)
         self.dets = torch.zeros((self.frames, self.C, self.R, 5), device=self.dev)
@@ -202,7 +207,7 @@ class DetectStep(_FrameGraphStep):
                 bbox_pred, agnostic, stds, means = torch.zeros((self.R, 4), device=self.dev), True, None, None
             ops.detection_postprocess(rois[0], cls_prob[0], bbox_pred.reshape(self.R, -1), 0.0, 0.0, 0.0, agnostic, stds, means,
                                       self.thresh, cfg.TEST.NMS, self.max_per_image, im_info=self.info[f],
-                                      out=(self.dets[f], self.counts[f]))
+                                      out=(self.dets[f], self.counts[f]), soft_nms=self.soft_nms)
 
     def stage(self, im_data, im_info):
         """``im_data``: (n,3,H,W) float frames (device or pinned host) or the (n,4,H,W) channels_last blob of the device
@@ -409,11 +414,11 @@ def trim_proposals(rois):
 
 @torch.no_grad()
 def detect_frame(net, im_data, im_info, gt_boxes, num_boxes, thresh=0.0, max_per_image=100, class_agnostic=False,
-                 keep_proposals=False):
+                 keep_proposals=False, soft_nms=None):
     """Returns ``all_boxes_i``: list over classes of (n_j, 5) float32 arrays [x1,y1,x2,y2,score] in original-image
     coordinates (entry 0, background, is empty) -- the reference's ``all_boxes[j][i]`` for this frame.  ``keep_proposals``:
     returns ``(all_boxes_i, proposals)``, the second the frame's (n, 4) float32 proposals in scaled-image coordinates
-    (``trim_proposals`` of ``rois``)."""
+    (``trim_proposals`` of ``rois``).  ``soft_nms``: as ``DetectStep``'s."""
     assert im_data.shape[0] == 1, "the reference evaluates one frame at a time (test_net_...:95 batch_size 1)"
     if hasattr(net, "forward_detect") and not net.training:
         out = net.forward_detect(im_data, im_info)        # the three outputs read below; the discriminators' are not computed
@@ -429,7 +434,7 @@ def detect_frame(net, im_data, im_info, gt_boxes, num_boxes, thresh=0.0, max_per
         bbox_pred = torch.zeros((R, 4), device=rois.device)
         class_agnostic, stds, means = True, None, None
     dets, counts = ops.detection_postprocess(rois, cls_prob, bbox_pred, info[0], info[1], info[2], class_agnostic, stds, means,
-                                             thresh, cfg.TEST.NMS, max_per_image)
+                                             thresh, cfg.TEST.NMS, max_per_image, soft_nms=soft_nms_options(soft_nms))
     counts = counts.cpu().numpy()                  # the one synchronisation of the frame
     dets = dets.cpu().numpy()
     res = [np.ascontiguousarray(dets[j, :counts[j]]) for j in range(C)]

@@ -261,6 +261,30 @@ def nms_sorted(dets, thresh, max_keep=0):
     return keep, num
 
 
+def soft_nms(dets, counts=None, method="linear", nt=0.3, sigma=0.5, min_score=0.001):
+    """Soft-NMS of independent sets on the device (``soft_nms.py`` has the rules).  dets (n,5) or (n_set,n,5), rows in descending
+    score order; counts (n_set,) int32 valid rows per set (None: all n) -> (out_dets (n_set,n,5) the emitted rows in emission order
+    with their final scores, out_src (n_set,n) int32 the input row of each, out_num (n_set,) int32), on the device (no sync);
+    rows behind ``out_num`` are not written.  n <= 4096."""
+    from . import soft_nms as sn
+    opt = sn.options((method, sigma, min_score))
+    _need_cuda(dets, counts)
+    d = dets.contiguous().float()
+    if d.dim() == 2:
+        d = d.unsqueeze(0)
+    n_set, n = d.shape[0], d.shape[1]
+    if counts is not None:
+        counts = counts.reshape(-1).to(torch.int32).contiguous()
+        if counts.numel() != n_set:
+            raise ValueError("soft_nms: %d counts for %d sets" % (counts.numel(), n_set))
+    out = torch.empty((n_set, max(n, 1), 5), device=d.device, dtype=torch.float32)
+    src = torch.empty((n_set, max(n, 1)), device=d.device, dtype=torch.int32)
+    num = torch.empty((n_set,), device=d.device, dtype=torch.int32)
+    check(lib.i2v_soft_nms(ptr(d), ptr(counts), n_set, n, sn.METHODS.index(opt.method), float(nt), opt.sigma, opt.min_score,
+                           ptr(out), ptr(src), ptr(num), None, 0, stream()), "soft_nms")
+    return out, src, num
+
+
 def sort_desc(keys):
     """(n_seg,n) fp32 -> int32 order (descending, ties by ascending index)."""
     _need_cuda(keys)
@@ -974,13 +998,15 @@ def dpixel(x_rows, w1, w2, w3, lamb=1.0, pix_per_roi=49, want_feat=False):
 
 
 def detection_postprocess(rois, cls_prob, bbox_pred, im_h, im_w, im_scale, class_agnostic=False, stds=None, means=None,
-                          score_thresh=0.0, nms_thresh=0.3, max_per_image=100, im_info=None, out=None):
+                          score_thresh=0.0, nms_thresh=0.3, max_per_image=100, im_info=None, out=None, soft_nms=None):
     """Per-class detection post-processing of one image on the device (test_net_instance_styleD_bilinear.py:151-221).
 
     rois (R,5) [batch_idx,x1,y1,x2,y2]; cls_prob (R,C); bbox_pred (R,4) or (R,4C).  ``stds`` / ``means``: the
     TRAIN.BBOX_NORMALIZE_STDS / _MEANS 4-tuples when the deltas are normalised, else None.  ``im_info``: the frame's
     [height, width, scale] as a device tensor of 3 floats, read by the kernel instead of the three host numbers (a
-    captured step: the same launch for every frame); ``out``: (dets, counts) buffers to write into.
+    captured step: the same launch for every frame); ``out``: (dets, counts) buffers to write into.  ``soft_nms``: None, the
+    greedy NMS (today's entries, unchanged); a method name, a (method, sigma, min_score) triple or a ``soft_nms.SoftNMS``:
+    Soft-NMS per class with ``Nt = nms_thresh`` (``soft_nms.py``), the image-wide cut then on the decayed scores.
     Returns (dets (C,R,5), counts (C,) int32), both on the device: rows ``dets[j, :counts[j]]`` are the reference's
     ``all_boxes[j][i]``."""
     import ctypes
@@ -1006,6 +1032,22 @@ def detection_postprocess(rois, cls_prob, bbox_pred, im_h, im_w, im_scale, class
         _need_cuda(im_info)
         if im_info.dtype != torch.float32 or im_info.numel() != 3 or not im_info.is_contiguous():
             raise ValueError("detection_postprocess(im_info=...): 3 contiguous floats on the device")
+    from . import soft_nms as sn
+    opt = sn.options(soft_nms)
+    if opt is not None:
+        soft = (sn.METHODS.index(opt.method), opt.sigma, opt.min_score)
+        if im_info is not None:
+            check(lib.i2v_det_postprocess_soft_info(ptr(rois), ptr(cls_prob), ptr(bbox_pred), int(bool(class_agnostic)), f4(stds),
+                                                    f4(means), ptr(im_info), R, C, float(score_thresh), float(nms_thresh),
+                                                    int(max_per_image), *soft, ptr(dets), ptr(counts), ptr(ws), ws.numel(), stream()),
+                  "det_postprocess_soft_info")
+        else:
+            check(lib.i2v_det_postprocess_soft(ptr(rois), ptr(cls_prob), ptr(bbox_pred), int(bool(class_agnostic)), f4(stds), f4(means),
+                                               float(im_h), float(im_w), float(im_scale), R, C, float(score_thresh), float(nms_thresh),
+                                               int(max_per_image), *soft, ptr(dets), ptr(counts), ptr(ws), ws.numel(), stream()),
+                  "det_postprocess_soft")
+        return dets, counts
+    if im_info is not None:
         check(lib.i2v_det_postprocess_info(ptr(rois), ptr(cls_prob), ptr(bbox_pred), int(bool(class_agnostic)), f4(stds), f4(means),
                                            ptr(im_info), R, C, float(score_thresh), float(nms_thresh), int(max_per_image),
                                            ptr(dets), ptr(counts), ptr(ws), ws.numel(), stream()), "det_postprocess_info")

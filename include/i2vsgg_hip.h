@@ -202,6 +202,48 @@ int32_t i2v_det_postprocess_info(const float* rois, const float* cls_prob, const
                                  int32_t R, int32_t C, float score_thresh, float nms_thresh, int32_t max_per_image,
                                  float* dets, int32_t* counts, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- Soft-NMS (Bodla et al., ICCV 2017; not in the reference: i2vsgg_amd/soft_nms.py states the rules) -----------
+ * dets (n_set, n, 5) fp32 rows [x1,y1,x2,y2,score] of n_set independent sets, each ALREADY in descending score order
+ * (equal scores in the order they should win); counts (n_set) int32 ON THE DEVICE: the valid rows of each set, or NULL:
+ * all n.  While live rows remain: the live row m with the largest current score (equal scores: the lowest row) is
+ * emitted with that score and retired; every other live row i, with iou = IoU(m, i) in the arithmetic of nms_cpu.py:14-29
+ * (fp32, +1 extents, inter / ((area_m + area_i) - inter)):
+ *   I2V_SOFT_NMS_HARD      iou > nt: dropped
+ *   I2V_SOFT_NMS_LINEAR    iou > nt: s_i = s_i * (1 - iou) in fp32
+ *   I2V_SOFT_NMS_GAUSSIAN  always (a NaN iou, 0 / 0 of two zero-area boxes, excepted): s_i = (float)((double)s_i *
+ *                          exp(-((double)iou * iou) / (double)sigma))
+ * and a row a decay was applied to is dropped when its score is then < min_score.
+ *   out_dets (n_set, n, 5) the emitted rows in emission order (scores non-increasing) with their final scores,
+ *   out_src (n_set, n) int32 the input row of each, out_num (n_set) int32 their count; rows behind it are not written.
+ * One workgroup per set, the set on chip throughout: n <= 4096, more is I2V_ERR_ARG.  hard and linear equal the host form
+ * bit for bit; gaussian in rows and order, its scores within one fp32 ulp per decay received (the float64 exp).
+ * No workspace is needed today (the query returns 0; NULL is accepted).  Fully asynchronous.
+ * i2v_soft_nms_plan: the launch for n rows of each of n_set sets.  Fields:
+ *    0 status   0 ok, 1 more than 4096 rows        1 form   0 WAVE (n <= 512: one wave, no barrier), 1 BLOCK (16 waves)
+ *    2 waves    3 rows per lane (1, 2, 4, 5, 8)    4 grid   5 threads   6 dynamic LDS bytes */
+#define I2V_SOFT_NMS_HARD      0
+#define I2V_SOFT_NMS_LINEAR    1
+#define I2V_SOFT_NMS_GAUSSIAN  2
+#define I2V_SOFT_NMS_PLAN_FIELDS 7
+size_t  i2v_soft_nms_workspace_bytes(int32_t n_set, int32_t n);
+int32_t i2v_soft_nms(const float* dets, const int32_t* counts, int32_t n_set, int32_t n, int32_t method, float nt,
+                     float sigma, float min_score, float* out_dets, int32_t* out_src, int32_t* out_num,
+                     void* workspace, size_t workspace_bytes, void* stream);
+int32_t i2v_soft_nms_plan(int32_t n_set, int32_t n, int32_t* out, int32_t n_out);
+/* i2v_det_postprocess / _info with Soft-NMS in place of the greedy NMS: per class, i2v_soft_nms(method, nt = nms_thresh,
+ * sigma, min_score) on the thresholded, sorted rows; the image-wide max_per_image cut then acts on the DECAYED scores.
+ * Same outputs and the same workspace query; R <= 4096. */
+int32_t i2v_det_postprocess_soft(const float* rois, const float* cls_prob, const float* bbox_pred, int32_t class_agnostic,
+                                 const float* stds, const float* means, float im_h, float im_w, float im_scale,
+                                 int32_t R, int32_t C, float score_thresh, float nms_thresh, int32_t max_per_image,
+                                 int32_t method, float sigma, float min_score,
+                                 float* dets, int32_t* counts, void* workspace, size_t workspace_bytes, void* stream);
+int32_t i2v_det_postprocess_soft_info(const float* rois, const float* cls_prob, const float* bbox_pred, int32_t class_agnostic,
+                                      const float* stds, const float* means, const float* im_info,
+                                      int32_t R, int32_t C, float score_thresh, float nms_thresh, int32_t max_per_image,
+                                      int32_t method, float sigma, float min_score,
+                                      float* dets, int32_t* counts, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- relation triplet ranking (eval) -----------------------------------
  * replaces the scoring loop and the argsort of detection_output (lib/utils.py:584-628): cell (i, r) of rel_score
  * (n_pairs, n_rel) is multiplied by conf[ixs[i]] and conf[ixo[i]] (two fp32 roundings) and the k largest cells are

@@ -13,6 +13,7 @@ import argparse
 import os
 import pickle
 import sys
+import time
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
@@ -23,13 +24,21 @@ import torch  # noqa: E402
 
 
 def parse_args(argv=None):
-    """(the detection test loop's arguments, limits, areas): the two flags of this script are taken out first."""
+    """(the detection test loop's arguments, limits, areas): the flags of this script are taken out first -- ``--limits``, ``--areas``
+    and ``--soft_nms {off,linear,gaussian}`` [``--soft_nms_sigma`` 0.5] [``--soft_nms_min_score`` 0.001]: Soft-NMS per class in the
+    post-processing (i2vsgg_amd/soft_nms.py, Nt = cfg.TEST.NMS) instead of the reference's NMS; default off.  The returned
+    namespace carries ``soft_nms``, the keyword of ``eval.detect_frame`` / ``eval.DetectStep``."""
     import test_instance_styled as td
     p = argparse.ArgumentParser(add_help=False)
     p.add_argument("--limits", nargs="+", type=lambda t: None if t == "all" else int(t), default=None)
     p.add_argument("--areas", nargs="+", default=None)
+    p.add_argument("--soft_nms", default="off", choices=["off", "linear", "gaussian"])
+    p.add_argument("--soft_nms_sigma", type=float, default=0.5)
+    p.add_argument("--soft_nms_min_score", type=float, default=0.001)
     own, rest = p.parse_known_args(argv)
-    return td.parse_args(rest), own.limits, own.areas
+    a = td.parse_args(rest)
+    a.soft_nms = None if own.soft_nms == "off" else (own.soft_nms, own.soft_nms_sigma, own.soft_nms_min_score)
+    return a, own.limits, own.areas
 
 
 def main(argv=None):
@@ -75,15 +84,16 @@ def main(argv=None):
             all_boxes[j][i] = per_class[j] if len(per_class[j]) else empty
         proposals[i] = rois.astype(np.float64) / np.float64(scale)
 
+    t0 = time.time()
     if a.frames <= 1:
         z, nb = torch.zeros(1, 1, 5, device=dev), torch.zeros(1, device=dev)
         for i, data in enumerate(loader):
             per_class, rois = ev.detect_frame(net, data[0].to(dev), data[1].to(dev), z, nb, thresh=a.thresh, max_per_image=a.max_per_image,
-                                              class_agnostic=a.class_agnostic, keep_proposals=True)
+                                              class_agnostic=a.class_agnostic, keep_proposals=True, soft_nms=a.soft_nms)
             keep(i, per_class, rois, data[1].reshape(-1)[2].item())
     else:
         step = ev.DetectStep(net, frames=a.frames, thresh=a.thresh, max_per_image=a.max_per_image, class_agnostic=a.class_agnostic,
-                             device=dev, use_graph=not a.no_graph, keep_proposals=True)
+                             device=dev, use_graph=not a.no_graph, keep_proposals=True, soft_nms=a.soft_nms)
         groups, order = {}, []
 
         def pack(g):
@@ -109,6 +119,8 @@ def main(argv=None):
         for k, (res, props) in enumerate(step.run(batches(), u8=u8)):
             for (i, scale), per_class, rois in zip(order[k], res, props):
                 keep(i, per_class, rois, scale)
+    dt = time.time() - t0
+    print("im_detect: %d images, %.2f ms per image (%.1f frames/s)" % (num_images, 1e3 * dt / max(num_images, 1), num_images / max(dt, 1e-9)))
     out_dir = os.path.join(a.output_dir, a.net, a.dataset)
     os.makedirs(out_dir, exist_ok=True)
     for name, obj in (("detections.pkl", all_boxes), ("proposals.pkl", proposals)):
